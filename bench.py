@@ -4,6 +4,7 @@ pair interactions/s of the direct O(N^2) softened-gravity + kick/drift step at
 N = 262 144 (fp32, exact rsqrt, Plummer-2D synthetic data), 1/2/4/8 GPUs.
 
     python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # also DIR/{pos,vel,acc}.npy after the last timed step
     python bench.py --gpus N --steps K --warmup W          # typed as is: see "Launching" below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -413,6 +414,29 @@ def cpu_baseline(ic, n, target_s=6.0):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, bodies, limit=DUMP_LIMIT_BYTES, seed=SEED):
+    """--dump-outputs: the state a caller of the timed path receives after its last step (``Simulation.sync()``: pos, vel and
+    acc of every body, float32) as <out_dir>/<name>.npy.  Above `limit` bytes in all, the same fixed, seeded sample of bodies
+    (ascending indices) is written for every array, with those indices beside them as sample_index.npy (float64, exact).
+    Returns the names written."""
+    arrays = {k: np.ascontiguousarray(bodies[k], dtype=np.float32) for k in ("pos", "vel", "acc")}
+    n = len(bodies)
+    per_body = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    if per_body * n > limit:
+        keep = limit // (per_body + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[idx]) for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(out / f"{k}.npy", a)
+    return sorted(arrays)
+
+
 EXIT_PARITY = 4      # exit status of every rank when the sharded trajectory fails its self-check
 
 
@@ -471,7 +495,13 @@ def parse_args(argv=None):
                          "self-checks, the N > 1 line.  A rehearsal of the code a node run executes, not a measurement")
     ap.add_argument("--no-safe-first", action="store_true",
                     help="multi-GPU: do not measure the plain all-gather / torch-driven configuration before anything else is tried")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: after the timed steps, write what a caller of the timed path receives (position, velocity and "
+                         "acceleration of every body after its last step) as DIR/<name>.npy, float32; above 64 MB a fixed, seeded sample")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.gpus > 1 or args.rehearse_sharded):
+        ap.error("--dump-outputs writes the outputs of the single-GPU path: use it with --gpus 1")
+    return args
 
 
 class UnshardedReference:
@@ -1387,6 +1417,9 @@ def main() -> None:
                         symmetry=not args.no_symmetry, uniform_mass=not args.general_mass, sym_chunks_per_item=args.chunks_per_item,
                         mass_scaling=scaling)
     m = timed_region(sim, args, 1, 0, lambda: None, torch.cuda.synchronize)
+    if args.dump_outputs:       # the state after the last timed step, before anything else steps this handle
+        names = dump_outputs(args.dump_outputs, sim.sync())
+        sys.stderr.write(f"[bench] --dump-outputs: {', '.join(names)} -> {args.dump_outputs}\n")
 
     # the settled rate, AFTER the timed region (never part of `value`)
     sustained = None

@@ -12,8 +12,8 @@
 // operators and `mag_sq` (main.cpp:108-154), `#include "Vec2.hpp"` (main.cpp:23) is a harmless repeat,
 // `std::vector<Node> SHARED_QUADTREE` (main.cpp:41) has its `Node`, and `simulation->quadtree.nodes`
 // (main.cpp:626) is this adaptor's always-empty node list (the force is a direct sum: there is no tree to
-// draw).  The UNMODIFIED main.cpp compiles against this header: tests/test_dropin_compile.py runs
-// `g++ -std=c++20 -fsyntax-only` on it.  Without the reference's headers on the path (stand-alone use, e.g.
+// draw).  The UNMODIFIED main.cpp compiles against this header: INTEGRATION.md §2 gives the
+// `g++ -std=c++20 -fsyntax-only` command that checks it.  Without the reference's headers on the path (stand-alone use, e.g.
 // sim_thread_example.cpp) minimal layout-identical `Vec2` / `Body` / `Node` are declared here instead.
 //
 // `Simulation()` starts, like the reference's, from uniform_disc(25000) with epsilon = 1 and the velocity

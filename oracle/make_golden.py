@@ -15,6 +15,9 @@ Fixtures (little-endian float32 .npy, columns x,y,vx,vy,ax,ay,mass,radius):
                              pins the velocity clamp and soft boundary of iterate() (Simulation.hpp:133-155)
   ref_direct_acc_{1024,4096}.npy   single REF-DIRECT force evaluation (n,2)
   ref_direct_acc_eps1_1024.npy     same with the reference's default eps = 1
+  ic_random_333.npy, ref_direct_random_333_s7.npy, ref_direct_acc_eps0_random_333.npy
+                             random (non-Plummer) bodies with a coincident pair: 7 REF-DIRECT steps
+                             (eps 0.3, dt 0.01) and one force evaluation at eps = 0
   fast_inv_sqrt_x.npy / _y.npy     Quadtree::fast_inv_sqrt on a fixed 4096-point grid
   layout.json                sizeof/alignof/offsetof of the compiled Body / Vec2
   default_ics.json           digest + first/last bodies of Simulation()'s own 25 000-body ICs
@@ -95,6 +98,22 @@ def main() -> None:
         assert ref.ref_step(c, c.shape[0], 1.0, 0.01, steps) == steps
         assert not c[:, 4:6].any()          # accelerations are exactly zero
         out[f"ref_step_extras_s{steps}.npy"] = c
+
+    # random (non-Plummer) inputs with a coincident pair (the r_sq > 0 guard): 7 REF-DIRECT steps at eps 0.3,
+    # dt 0.01, and one force evaluation at eps = 0
+    rng = np.random.default_rng(5)
+    rnd = np.zeros((333, 8), np.float32)
+    rnd[:, 0:2] = rng.normal(size=(333, 2)) * 3
+    rnd[:, 2:4] = rng.normal(size=(333, 2))
+    rnd[:, 6] = rng.uniform(0.1, 2.0, 333)
+    rnd[7, 0:2] = rnd[8, 0:2]
+    out["ic_random_333.npy"] = rnd.copy()
+    a = np.ascontiguousarray(rnd.copy())
+    ref.ref_direct_step(a, a.shape[0], 0.3, 0.01, 7, 0)
+    out["ref_direct_random_333_s7.npy"] = a
+    a = np.ascontiguousarray(rnd.copy())
+    ref.ref_direct_acc(a, a.shape[0], 0.0)
+    out["ref_direct_acc_eps0_random_333.npy"] = np.ascontiguousarray(a[:, 4:6])
 
     x = np.concatenate([
         np.logspace(-12, 12, 2048).astype(np.float32),

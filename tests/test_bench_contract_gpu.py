@@ -203,3 +203,29 @@ def test_launched_ranks_that_cannot_form_a_group_fall_back_to_one_process():
     assert d["n_gpus"] == 2 and d["parity_check"]["ok"] is True and d["fallback"] == {"used": False} and "in-process" in d["config"]["backend"]
     assert r.stderr.count("starting 2 ranks as child processes") == 2 and "one more attempt" in r.stderr
     assert "falling back to ONE process driving all 2 handles" in r.stderr
+
+
+def test_dump_outputs_is_the_state_after_the_last_timed_step(tmp_path):
+    """--dump-outputs: pos / vel / acc after warm-up + K timed steps, the same bits from run to run and the same bits as a handle of
+    the same system stepped as often; --steps really is the number of timed steps."""
+    import numpy as np
+
+    import nbodysim_amd as nb
+    fast = ("--nbodies", "16384", "--warmup", "1", "--no-cpu-baseline", "--no-live-pmc", "--no-secondary", "--no-sustained")
+    runs = {}
+    for tag, steps in (("a", 3), ("b", 3), ("c", 4)):
+        d = run_bench(*fast, "--steps", str(steps), "--dump-outputs", str(tmp_path / tag))
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        runs[tag] = {k: np.load(tmp_path / tag / f"{k}.npy") for k in ("pos", "vel", "acc")}
+        assert sorted(p.name for p in (tmp_path / tag).iterdir()) == ["acc.npy", "pos.npy", "vel.npy"]
+    for k, a in runs["a"].items():
+        assert a.dtype == np.float32 and a.shape == (16384, 2) and np.isfinite(a).all()
+        assert np.array_equal(a.view(np.uint32), runs["b"][k].view(np.uint32)), k
+    assert not np.array_equal(runs["a"]["pos"], runs["c"]["pos"])
+    ic = nb.plummer_2d(16384, 42)
+    for tag, total in (("a", 1 + 3), ("c", 1 + 4)):
+        with nb.Simulation(ic, eps=0.01, device=0) as sim:
+            sim.advance(total, 1e-3)
+            got = sim.sync()
+            for k, a in runs[tag].items():
+                assert np.array_equal(a.view(np.uint32), np.ascontiguousarray(got[k]).view(np.uint32)), (tag, k)

@@ -192,3 +192,42 @@ def test_typed_without_a_launcher_the_ranks_start_as_children_even_here():
         assert r.returncode != 0 and r.stderr.count("bench.py needs a GPU") >= 1 and r.stdout.strip() == ""
         # ... and the last resort was tried too: ONE process driving all handles (which, here, finds no GPU either)
         assert "falling back to ONE process driving all 2 handles" in r.stderr and r.stderr.rstrip().endswith("the hot path has no CPU fallback")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------------
+def test_dump_outputs_writes_every_body_or_a_fixed_sample_within_the_limit(tmp_path):
+    import numpy as np
+    from nbodysim_amd import bodies_array
+    b = load_bench()
+    n = 5000
+    bodies = bodies_array(n)
+    rng = np.random.default_rng(1)
+    for k in ("pos", "vel", "acc"):
+        bodies[k] = rng.normal(size=(n, 2)).astype(np.float32)
+    assert b.dump_outputs(tmp_path / "all", bodies) == ["acc", "pos", "vel"]
+    for k in ("pos", "vel", "acc"):
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, bodies[k])
+    # above the limit: the same seeded sample of bodies in every array, its indices beside them, the whole within the limit
+    limit = 40_000
+    assert b.dump_outputs(tmp_path / "s1", bodies, limit=limit) == ["acc", "pos", "sample_index", "vel"]
+    b.dump_outputs(tmp_path / "s2", bodies, limit=limit)
+    idx = np.load(tmp_path / "s1" / "sample_index.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) < n and (np.diff(idx) > 0).all()
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "sample_index.npy"))
+    assert sum(np.load(p).nbytes for p in (tmp_path / "s1").glob("*.npy")) <= limit
+    for k in ("pos", "vel", "acc"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), bodies[k][idx.astype(np.int64)])
+    # the headline size stays whole
+    assert 262_144 * 24 <= b.DUMP_LIMIT_BYTES == 64 << 20
+
+
+def test_dump_outputs_is_for_the_single_gpu_path():
+    import pytest
+    b = load_bench()
+    assert b.parse_args(["--dump-outputs", "d"]).dump_outputs == "d" and b.parse_args([]).dump_outputs is None
+    for argv in (["--gpus", "2", "--dump-outputs", "d"], ["--rehearse-sharded", "--dump-outputs", "d"]):
+        with pytest.raises(SystemExit):
+            b.parse_args(argv)
