@@ -22,6 +22,7 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include <unistd.h>
@@ -55,6 +56,15 @@ extern "C" int nb_device_count(void)
 struct ForceJob { uint32_t j_begin, j_end, js, slab0; int P; uint32_t i_tiles; uint32_t gap_begin, gap_len; };
 
 constexpr int F32_WS = 4;   // waves of a workgroup sharing one i-set in force_tiled_f32 (in-workgroup j-split)
+
+// How a handle computes a step: chosen once by nb_create (step_path_of) and never changed.
+enum class StepPath {
+    SYM,              // the whole system on this handle, symmetric kernel (force_sym_*)
+    SYM_SHARDED,      // symmetric, this rank's share of the pairs; the host reduce-scatters acc_full into acc_owned
+    SYM_REPLICATED,   // symmetric, this rank's share of the pairs; the host all-reduces acc_full and every rank integrates all n
+    TWO_PHASE,        // one-sided, sharded: the owned j-block first (beside the exchange), then the rest
+    ONE_SIDED,        // one-sided over job_all
+};
 
 struct nb_sim {
     nb_params p;
@@ -96,13 +106,13 @@ struct nb_sim {
     bool acc_valid = false;         // KDK: acc holds a(x_cur)
     bool uniform_mass = false;      // every body has the same mass: the per-pair mass multiply is hoisted
     float um_mass = 0.f;
-    bool sym_pairs = false;         // symmetric fp32 kernel sweeps chunk pairs (want_pairs)
+    bool sym_pairs = false;         // the symmetric plan has even chunk counts (want_pairs); sym_uses_pairs decides the kernel
     bool mass_scaled = false;       // individual masses folded into the pair geometry (MM_SCALED, nb_kernels.hip.h)
     float *sigma = nullptr;         // m^(-1/2) per particle, for mass_scaled
     float mass_scaling_dev = -1.0f; // what the upload-time check measured: max |a_scaled - a_general| / max |a_general| (-1: not measured)
 
-    // symmetric path (force_sym_f32): work items and its two slab sets
-    bool sym = false;
+    StepPath path = StepPath::ONE_SIDED;
+    // symmetric paths (force_sym_f32): work items and its two slab sets
     uint32_t sym_items = 0, sym_items_local = 0, sym_items_cross = 0, sym_items_late = 0;   // [local | cross | late]
     uint32_t sym_tiles = 0, sym_rows = 0, sym_L = 0, sym_cov_late_off = 0;
     uint32_t sym_sb = SYM_SB, sym_sb_shift = 11;   // particles per block-tile of the plan: 2048 (classic) or 512 (wave-split kernels)
@@ -119,12 +129,9 @@ struct nb_sim {
                                                // 128 bytes apart — a sharded rank's launches may run side by side)
     uint32_t sym_first_wave = 0;               // workgroups that keep their static item (the resident slots of the kernel variant); 0 = not yet known
     bool sym_first_wave_uniform = false, sym_first_wave_scaled = false;   // the mass model of the instantiation it was asked for (do_upload resets it on a change)
-    // symmetric SHARDED protocol: this rank holds the items of the tiles dealt to it
-    bool sym_sharded = false;
-    // symmetric REPLICATED protocol (NB_FLAG_SHARD_ALLREDUCE): the handle holds this rank's share of the pairs like a
-    // sharded one, but integrates ALL n particles itself after the host has all-reduced the partial accelerations:
-    // one collective per step, every rank keeps the whole (bit-identical) state
-    bool sym_replicated = false;
+    // SYM_SHARDED: this rank holds the items of the tiles dealt to it.  SYM_REPLICATED (NB_FLAG_SHARD_ALLREDUCE): the handle
+    // holds this rank's share of the pairs like a sharded one, but integrates ALL n particles itself after the host has
+    // all-reduced the partial accelerations: one collective per step, every rank keeps the whole (bit-identical) state
     void *acc_full = nullptr, *acc_owned = nullptr;     // reduce-scatter input (n) / output (i_count), (ax,ay) reals
     bool own_acc = true;
     // the local items run on a side stream so that their tail and the head of the cross items share the chip
@@ -156,14 +163,53 @@ static int bind(const nb_sim *s)
     return NB_OK;
 }
 
+// ---------------------------------------------------------------------------
+// dispatch: run-time choices -> template arguments
+// ---------------------------------------------------------------------------
+// Element layout of a handle: real type, the vector of one position / velocity / acceleration / slab element
+// (real2 in 2-D, real4 {x,y,z,m} in 3-D), and whether it is 3-D.  2-D handles also keep a separate `mass` array.
+template <typename R, bool D3>
+struct Layout {
+    using real = R;
+    using vec = std::conditional_t<D3, typename vec4_of<R>::type, typename vec2_of<R>::type>;
+    static constexpr bool dims3 = D3;
+};
+
+// f(Layout<...>{}) for the handle's precision and dimensionality: the one place that maps them to types.
+template <typename F>
+static auto with_layout(const nb_sim *s, F &&f)
+{
+    if (s->dims3) return s->fp64 ? f(Layout<double, true>{}) : f(Layout<float, true>{});
+    return s->fp64 ? f(Layout<double, false>{}) : f(Layout<float, false>{});
+}
+
+// f(std::bool_constant<b>...) for the run-time flags b...
+template <typename F>
+static auto with_flags(F &&f) { return f(); }
+
+template <typename F, typename... B>
+static auto with_flags(F &&f, bool b, B... rest)
+{
+    if (b) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+    return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
+// f(std::integral_constant<int, P>{}) for P in {1, 2, 4}; PMAX = 2 for the fp64 kernels, which have no P = 4.
+template <int PMAX, typename F>
+static auto with_lanes(int P, F &&f)
+{
+    if constexpr (PMAX >= 4)
+        if (P == 4) return f(std::integral_constant<int, 4>{});
+    if (P == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 1>{});
+}
+
 // Launch geometry of one one-sided force job.  The kernel is VALU-bound, so what
 // matters is (a) enough independent work per lane — 2P particles per lane, P = 4 measured best — and
 // (b) enough workgroups in flight to keep 5-8 waves per SIMD issuing and to even out the tail: about
 // 32 workgroups per CU (profiles/history/r01_force_tiled_geometry_sweep.log).  When i-particles are scarce (sharded or small runs)
 // the j range is cut into more tile-aligned slices (at most 128: every slice is a slab that
 // `integrate` re-reads), and P drops only when even that cannot fill half the target.
-static bool want_sym(const nb_sim *s);
-
 // Slices are whole LDS tiles and none is empty: js = ceil(tiles / ceil(tiles / want)).
 static uint32_t even_slices(uint32_t jn, uint32_t want)
 {
@@ -213,7 +259,7 @@ static void plan(nb_sim *s)
 {
     const uint32_t n = (uint32_t)s->n, ib = (uint32_t)s->i_begin, ic = (uint32_t)s->i_count;
     s->job_all = plan_job(s, 0, n, 0);
-    s->slabs_all = s->sym ? 1 : s->job_all.js;           // the symmetric path leaves one summed slab
+    s->slabs_all = s->path == StepPath::SYM ? 1 : s->job_all.js;   // the symmetric path leaves one summed slab
     s->job_local = plan_job(s, ib, ib + ic, 0);
     // everything but the owned block, in one launch: virtual j range [0, n - ic) with a gap at the block
     s->job_remote = plan_job(s, 0, n - ic, s->job_local.js, ib, ic);
@@ -279,26 +325,27 @@ static bool single_rank(const nb_sim *s)
     return (s->p.flags & NB_FLAG_SHARD_SINGLE) && s->p.shard_world == 1 && s->p.shard_rank == 0 && s->i_count == s->n;
 }
 
-static bool want_sym(const nb_sim *s)          // single handle owns everything
+// Decided once, before nb_create allocates the handle's buffers (sym_eligible looks at the free device memory, which they change).
+static StepPath step_path_of(const nb_sim *s)
 {
-    return s->i_count == s->n && s->p.shard_world <= 1 && !single_rank(s) && sym_eligible(s);
+    const bool whole = s->i_count == s->n;
+    if (sym_eligible(s)) {
+        const bool kick_drift = s->p.integrator == NB_INTEGRATOR_KICK_DRIFT, allreduce = (s->p.flags & NB_FLAG_SHARD_ALLREDUCE) != 0;
+        const size_t w = (size_t)s->p.shard_world;
+        if (single_rank(s)) {
+            if (kick_drift) return allreduce ? StepPath::SYM_REPLICATED : StepPath::SYM_SHARDED;
+        } else if (s->p.shard_world <= 1) {
+            if (whole) return StepPath::SYM;                   // single handle owns everything
+        } else if (s->n / w >= 2 * (size_t)SYM_SB && s->n % (w * SYM_SB) == 0) {
+            // replicated: every rank holds (and integrates) everything; sharded: equal blocks of whole tiles
+            if (whole && allreduce && kick_drift) return StepPath::SYM_REPLICATED;
+            if (!whole && s->i_count == s->n / w && s->i_begin == (size_t)s->p.shard_rank * s->i_count) return StepPath::SYM_SHARDED;
+        }
+    }
+    return !whole && s->p.sum_order != NB_SUM_SEQUENTIAL ? StepPath::TWO_PHASE : StepPath::ONE_SIDED;
 }
 
-static bool want_sym_replicated(const nb_sim *s)  // rank of a run that all-reduces accelerations and integrates everything everywhere
-{
-    const size_t w = (size_t)s->p.shard_world;
-    if (!(s->p.flags & NB_FLAG_SHARD_ALLREDUCE) || s->i_count != s->n || s->p.integrator != NB_INTEGRATOR_KICK_DRIFT || !sym_eligible(s)) return false;
-    if (single_rank(s)) return true;
-    return s->p.shard_world > 1 && s->n / w >= 2 * (size_t)SYM_SB && s->n % (w * SYM_SB) == 0;
-}
-
-static bool want_sym_sharded(const nb_sim *s)  // rank of a sharded run
-{
-    const size_t w = (size_t)s->p.shard_world;
-    if (single_rank(s)) return !(s->p.flags & NB_FLAG_SHARD_ALLREDUCE) && s->p.integrator == NB_INTEGRATOR_KICK_DRIFT && sym_eligible(s);
-    return s->p.shard_world > 1 && s->i_count != s->n && sym_eligible(s) && s->n / w >= 2 * (size_t)SYM_SB &&
-           s->n % (w * SYM_SB) == 0 && s->i_count == s->n / w && s->i_begin == (size_t)s->p.shard_rank * s->i_count;   // equal blocks of whole tiles
-}
+static bool symmetric(const nb_sim *s) { return s->path == StepPath::SYM || s->path == StepPath::SYM_SHARDED || s->path == StepPath::SYM_REPLICATED; }
 
 // Chunk-units of local work a rank holds back to run beside the reduce-scatter: 40 us of whole-chip work at the
 // measured 35 units/us (fp32) or 14 (fp64) of 256 CUs.  Alone on the chip those items take 50-60 us and the
@@ -321,7 +368,17 @@ static bool want_pairs(const nb_params &p, size_t n)
 {
     if (p.precision == NB_FP64) return false;
     if (p.sym_chunk_pairs) return p.sym_chunk_pairs > 0;
-    return n >= 65536;                           // 2-D and 3-D (3-D with individual masses keeps the single-chunk kernel: launch_sym_items)
+    return n >= 65536;                           // 2-D and 3-D (3-D with individual masses keeps the single-chunk kernel: sym_uses_pairs)
+}
+
+// Whether the symmetric launch runs the chunk-pair kernel (any plan, even chunk counts included, runs on either kernel).
+// 2-D: not with MM_SCALED.  3-D: chunk pairs pay with equal masses only (-1 ... -3 %); with individual masses the pair body
+// needs 216 VGPRs (2 waves per SIMD) and loses 4 % (profiles/history/r03_chunk_pairs_3d.log): that case keeps the
+// single-chunk sweep unless nb_params.sym_chunk_pairs = 1 forces it.
+static bool sym_uses_pairs(const nb_sim *s)
+{
+    if (!s->sym_pairs) return false;
+    return s->dims3 ? s->uniform_mass || s->p.sym_chunk_pairs > 0 : !s->mass_scaled;
 }
 
 static SymTuning tuning_of(const nb_params &p, bool fp64, int cus, uint32_t world, bool sharded, size_t n)
@@ -516,11 +573,11 @@ static int copy_d2h(nb_sim *s, void *dst, const void *src, size_t bytes, hipStre
 static int plan_sym(nb_sim *s)
 {
     const uint32_t n = (uint32_t)s->n;
-    const bool split = s->sym_sharded || s->sym_replicated;
+    const bool sharded = s->path == StepPath::SYM_SHARDED, split = s->path != StepPath::SYM;
     const uint32_t world = split ? (uint32_t)s->p.shard_world : 1u;
     const uint32_t rank = split ? (uint32_t)s->p.shard_rank : 0u;
     SymPlan pl;
-    build_sym_plan(n, (uint32_t)s->cus, rank, world, tuning_of(s->p, s->fp64, s->cus, world, s->sym_sharded, s->n), pl);   // late items: sharded only
+    build_sym_plan(n, (uint32_t)s->cus, rank, world, tuning_of(s->p, s->fp64, s->cus, world, sharded, s->n), pl);   // late items: sharded only
     s->sym_pairs = want_pairs(s->p, s->n);
     const uint32_t tiles = pl.tiles, row = pl.rowbase[tiles];
     s->sym_info.struct_size = (uint32_t)sizeof(nb_sym_info);
@@ -554,7 +611,7 @@ static int plan_sym(nb_sim *s)
     // on 512 resident slots, 150 us where 128 us of work is due): run concurrently, the cross items fill the CUs
     // the last local workgroups leave idle (-1.7 % step time; with two LONG launches sharing the chip, P = 2, the
     // same trick costs 4 % — profiles/history/r01_aux_stream_ab.log — hence the bound).  nb_params.sym_aux_stream = 1 / -1 forces it.
-    s->aux_local = s->sym_sharded && (s->p.sym_aux_stream ? s->p.sym_aux_stream > 0 : s->sym_items_local <= 4u * (uint32_t)s->cus);
+    s->aux_local = sharded && (s->p.sym_aux_stream ? s->p.sym_aux_stream > 0 : s->sym_items_local <= 4u * (uint32_t)s->cus);
     if (s->aux_local || s->sym_items_late) {         // the late items always run on the side stream
         HIPCHK(hipStreamCreateWithFlags(&s->aux, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
@@ -565,7 +622,7 @@ static int plan_sym(nb_sim *s)
         if (s->p.acc_buffers[0]) { s->acc_full = s->p.acc_buffers[0]; s->acc_owned = s->p.acc_buffers[1]; s->own_acc = false; }
         else {
             HIPCHK(hipMalloc(&s->acc_full, (size_t)n * s->esz));
-            if (s->sym_sharded) HIPCHK(hipMalloc(&s->acc_owned, s->i_count * s->esz));
+            if (sharded) HIPCHK(hipMalloc(&s->acc_owned, s->i_count * s->esz));
         }
     }
     return NB_OK;
@@ -602,7 +659,7 @@ static void free_all(nb_sim *s)
 }
 
 static int launch_force(nb_sim *s, const ForceJob &j);
-static int launch_integrate(nb_sim *s, uint32_t nslabs, double dt_kick, double dt_drift, int flags);
+static int integrate_slabs(nb_sim *s, uint32_t nslabs, double dt_kick, double dt_drift, int flags);
 
 // The MEASURED rule of the mass-scaled body (NB_FLAG_MASS_SCALING_MEASURED; opt-in since ABI 6): decided per upload FROM THE
 // DATA.  The accelerations of the uploaded bodies are evaluated twice — with the per-pair mass multiplies (MM_GENERAL) and with
@@ -633,10 +690,10 @@ static int choose_mass_scaling(nb_sim *s)
         HIPCHK(hipMemsetAsync(out, 0, 2 * sizeof(uint32_t), s->stream));
         int r;
         s->mass_scaled = false;
-        if ((r = launch_force(s, s->job_all)) || (r = launch_integrate(s, s->slabs_all, 0.0, 0.0, 0))) return r;
+        if ((r = launch_force(s, s->job_all)) || (r = integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0))) return r;
         HIPCHK(hipMemcpyAsync(ref, s->acc, bytes, hipMemcpyDeviceToDevice, s->stream));
         s->mass_scaled = true;
-        if ((r = launch_force(s, s->job_all)) || (r = launch_integrate(s, s->slabs_all, 0.0, 0.0, 0))) return r;
+        if ((r = launch_force(s, s->job_all)) || (r = integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0))) return r;
         max_deviation_f32<<<(n + BLOCK - 1) / BLOCK, BLOCK, 0, s->stream>>>((const float2 *)s->acc, (const float2 *)ref, n, out);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(s->acc, saved, bytes, hipMemcpyDeviceToDevice, s->stream));
@@ -708,27 +765,22 @@ static int do_upload(nb_sim *s, const nb_body *in)
         scalable = finite && mmin >= 1e-30 && std::pow(mmax, 1.5) / (eps * eps * eps) <= 1e36;
     }
     const bool forced_scaling = scalable && (s->p.flags & NB_FLAG_MASS_SCALING);
-    const bool auto_scaling = scalable && !forced_scaling && (s->p.flags & NB_FLAG_MASS_SCALING_MEASURED) && s->i_count == s->n && !s->sym_sharded && !s->sym_replicated;
+    const bool auto_scaling = scalable && !forced_scaling && (s->p.flags & NB_FLAG_MASS_SCALING_MEASURED) && s->i_count == s->n &&
+                             s->path != StepPath::SYM_SHARDED && s->path != StepPath::SYM_REPLICATED;
     const bool was_uniform = s->sym_first_wave_uniform, was_scaled = s->sym_first_wave_scaled;
     { const int rc = copy_h2d(s, s->aos_dev, in, s->n * sizeof(nb_body)); if (rc) return rc; }
-    const uint32_t n = (uint32_t)s->n, g = (n + BLOCK - 1) / BLOCK;
-    // both replicas get the full initial positions
-    for (int b = 0; b < 2; ++b) {
-        if (s->dims3 && s->fp64)
-            unpack_bodies3<double><<<g, BLOCK, 0, s->stream>>>(s->aos_dev, n, (double4 *)s->pos[b], (double4 *)s->vel, (double4 *)s->acc, s->radius,
-                                                               (uint32_t)s->i_begin, (uint32_t)s->i_count);
-        else if (s->dims3)
-            unpack_bodies3<float><<<g, BLOCK, 0, s->stream>>>(s->aos_dev, n, (float4 *)s->pos[b], (float4 *)s->vel, (float4 *)s->acc, s->radius,
-                                                              (uint32_t)s->i_begin, (uint32_t)s->i_count);
-        else if (s->fp64)
-            unpack_bodies<double><<<g, BLOCK, 0, s->stream>>>(s->aos_dev, n, (double2 *)s->pos[b], (double *)s->mass,
-                                                             (double2 *)s->vel, (double2 *)s->acc, s->radius,
-                                                             (uint32_t)s->i_begin, (uint32_t)s->i_count);
-        else
-            unpack_bodies<float><<<g, BLOCK, 0, s->stream>>>(s->aos_dev, n, (float2 *)s->pos[b], (float *)s->mass,
-                                                            (float2 *)s->vel, (float2 *)s->acc, s->radius,
-                                                            (uint32_t)s->i_begin, (uint32_t)s->i_count);
-    }
+    const uint32_t n = (uint32_t)s->n, g = (n + BLOCK - 1) / BLOCK, ib = (uint32_t)s->i_begin, ic = (uint32_t)s->i_count;
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        for (int b = 0; b < 2; ++b) {      // both replicas get the full initial positions
+            if constexpr (L.dims3)
+                unpack_bodies3<real><<<g, BLOCK, 0, s->stream>>>(s->aos_dev, n, (vec *)s->pos[b], (vec *)s->vel, (vec *)s->acc, s->radius, ib, ic);
+            else
+                unpack_bodies<real><<<g, BLOCK, 0, s->stream>>>(s->aos_dev, n, (vec *)s->pos[b], (real *)s->mass, (vec *)s->vel, (vec *)s->acc,
+                                                                s->radius, ib, ic);
+        }
+    });
     HIPCHK(hipGetLastError());
     if (forced_scaling || auto_scaling) {
         if (!s->sigma) HIPCHK(hipMalloc((void **)&s->sigma, s->n * sizeof(float)));
@@ -827,11 +879,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     if (p.stream) { s->stream = (hipStream_t)p.stream; s->own_stream = false; }
     else { if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e); s->own_stream = true; }
 
-    // decided once (eligibility looks at the free device memory, which the allocations below change)
-    s->sym = want_sym(s);
-    s->sym_sharded = want_sym_sharded(s);
-    s->sym_replicated = want_sym_replicated(s);
-    if (s->sym_replicated) s->sym = false;          // the whole-system plan is not built: this rank evaluates its share only
+    s->path = step_path_of(s);
     plan(s);
     const size_t r2 = s->esz;
     if (p.pos_buffers[0]) { s->pos[0] = p.pos_buffers[0]; s->pos[1] = p.pos_buffers[1]; s->own_pos = false; s->pos_rows = p.pos_rows ? (size_t)p.pos_rows : n; }
@@ -856,7 +904,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     s->ered_blocks = (s->i_count + BLOCK - 1) / BLOCK;
     if ((e = hipMalloc((void **)&s->ered_dev, 2 * s->ered_blocks * sizeof(double))) != hipSuccess) return fail("hipMalloc energy", e);
 
-    if ((s->sym || s->sym_sharded || s->sym_replicated) && plan_sym(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
+    if (symmetric(s) && plan_sym(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
     if (do_upload(s, init) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
     return s;
 }
@@ -915,43 +963,35 @@ static int prof_collect(nb_sim *s)
 // ---------------------------------------------------------------------------
 // force launch
 // ---------------------------------------------------------------------------
-template <int P, int RSQ, bool GUARD>
-static void launch_tiled_f32(nb_sim *s, const ForceJob &j, float eps2)
+// Launch of one symmetric force kernel over `count` items, with its dynamic work items (sym_item_index, nb_kernels.hip.h): past
+// the first resident wave — the resident slots of THIS kernel — a workgroup draws its item when it starts.  One counter per launch
+// kind of the handle (`slot`), monotonic: `tb` = what the launches of that kind have drawn so far.
+template <typename... KArgs, typename... Args>
+static int launch_sym_kernel(nb_sim *s, void (*kernel)(KArgs...), uint32_t count, uint32_t slot, hipStream_t st, Args... args)
 {
-    const uint32_t i_tiles = j.i_tiles;
-    const uint32_t grid = grid_blocks(i_tiles, j.js);
-    float2 *out = (float2 *)s->partial + (size_t)j.slab0 * s->i_count;
-    if constexpr (!GUARD) {
-        if (s->uniform_mass) {
-            force_tiled_f32<P, RSQ, false, 8, true, F32_WS><<<grid, BLOCK, 0, s->stream>>>(
-                (const float2 *)s->pos[s->cur], (const float *)s->mass, s->sigma, out,
-                (uint32_t)s->i_begin, (uint32_t)s->i_count, j.j_begin, j.j_end, j.js, i_tiles, eps2, s->um_mass,
-                j.gap_begin, j.gap_len);
-            return;
+    uint32_t *tk = nullptr;
+    uint32_t fw = 0, tb = 0, drawn = 0;      // drawn: tickets this launch will take — committed to the host's record only once the launch is known to be enqueued
+    if (s->sym_ticket != nullptr && !(s->p.flags & NB_FLAG_STATIC_ITEMS)) {
+        if (!s->sym_first_wave) {
+            int per_cu = 0;
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BLOCK, 0));
+            s->sym_first_wave = (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)s->cus;
         }
-        if constexpr (RSQ == RSQ_EXACT) {
-            if (s->mass_scaled) {      // individual masses folded into the pair geometry: no mass multiply in the body
-                force_tiled_f32<P, RSQ_EXACT, false, 8, false, F32_WS, true><<<grid, BLOCK, 0, s->stream>>>(
-                    (const float2 *)s->pos[s->cur], (const float *)s->mass, s->sigma, out,
-                    (uint32_t)s->i_begin, (uint32_t)s->i_count, j.j_begin, j.j_end, j.js, i_tiles, eps2, 1.0f, j.gap_begin, j.gap_len);
-                return;
-            }
-        }
+        fw = s->sym_first_wave < count ? s->sym_first_wave : count;
+        tk = s->sym_ticket + slot * 32u; tb = s->sym_ticket_base[slot];
+        drawn = count - fw;
     }
-    force_tiled_f32<P, RSQ, GUARD, 8, false, F32_WS><<<grid, BLOCK, 0, s->stream>>>(
-        (const float2 *)s->pos[s->cur], (const float *)s->mass, s->sigma, out,
-        (uint32_t)s->i_begin, (uint32_t)s->i_count, j.j_begin, j.j_end, j.js, i_tiles, eps2, 1.0f, j.gap_begin, j.gap_len);
-}
-
-template <int P, bool GUARD>
-static void launch_tiled_f64(nb_sim *s, const ForceJob &j, double eps2)
-{
-    const uint32_t i_tiles = j.i_tiles;
-    const uint32_t grid = grid_blocks(i_tiles, j.js);
-    double2 *out = (double2 *)s->partial + (size_t)j.slab0 * s->i_count;
-    force_tiled_f64<P, GUARD, 4><<<grid, BLOCK, 0, s->stream>>>(
-        (const double2 *)s->pos[s->cur], (const double *)s->mass, out,
-        (uint32_t)s->i_begin, (uint32_t)s->i_count, j.j_begin, j.j_end, j.js, i_tiles, eps2, j.gap_begin, j.gap_len);
+    kernel<<<count, BLOCK, 0, st>>>(args..., tk, fw, tb);
+    // The host's record of the tickets advances only with a launch that was accepted: if this one was refused, the device
+    // counter did not move either, but a kernel of an EARLIER launch may still be drawing — nothing sound can follow on
+    // this handle, so it is refused from here on (nb_step_begin) instead of indexing items[] with a base that may be off.
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        s->broken = true;
+        return nb_fail(hip_code(e), "launch of the symmetric force kernel failed: %s; the handle is unusable from here on", hipGetErrorString(e));
+    }
+    s->sym_ticket_base[slot] += drawn;
+    return NB_OK;
 }
 
 // Symmetric kernel over items [first, first + count) of this handle (HIP events around the launch
@@ -964,94 +1004,61 @@ static int launch_sym_items(nb_sim *s, uint32_t first, uint32_t count, hipStream
     if (s->prof && prof_begin(s, &pr, st)) return NB_EHIP;
     const uint32_t n = (uint32_t)s->n;
     const SymItem *items = s->sym_items_dev + first;
-    const bool quake = s->p.rsqrt_mode == NB_RSQRT_QUAKE;
-    // Dynamic work items (sym_item_index, nb_kernels.hip.h): past the first resident wave a workgroup draws its item when it starts.
-    // One counter per launch kind of the handle (this launch's is told by where its items begin), monotonic: `tb` = what the launches
-    // of that kind have drawn so far.
-    const uint32_t slot = first == 0 ? 0u : (first == s->sym_items_local ? 1u : 2u);
-    const bool dyn = s->sym_ticket != nullptr && !(s->p.flags & NB_FLAG_STATIC_ITEMS);
-    uint32_t *tk = nullptr;
-    uint32_t fw = 0, tb = 0, drawn = 0;      // drawn: tickets this launch will take — committed to the host's record only once the launch is known to be enqueued
-#define NB_TICKETS(KERNEL)                                                                                                        \
-    do {                                                                                                                          \
-        if (dyn) {                                                                                                                \
-            if (!s->sym_first_wave) {                                                                                             \
-                int per_cu = 0;                                                                                                   \
-                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, BLOCK, 0));                                  \
-                s->sym_first_wave = (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)s->cus;                                       \
-            }                                                                                                                     \
-            fw = s->sym_first_wave < count ? s->sym_first_wave : count;                                                           \
-            tk = s->sym_ticket + slot * 32u; tb = s->sym_ticket_base[slot];                                                       \
-            drawn = count - fw;                                                                                                   \
-        }                                                                                                                         \
-    } while (0)
-    if (s->dims3 && s->fp64) {
-        const double eps2 = (double)s->p.eps * (double)s->p.eps;
-        const double4 *pos = (const double4 *)s->pos[s->cur];
-        double4 *ss = (double4 *)s->sym_slab_s, *sr = (double4 *)s->sym_slab_r;
-        if (s->uniform_mass) { NB_TICKETS(force_sym3_f64<true>);  force_sym3_f64<true><<<count, BLOCK, 0, st>>>(pos, items, ss, sr, n, eps2, (double)s->um_mass, tk, fw, tb); }
-        else                 { NB_TICKETS(force_sym3_f64<false>); force_sym3_f64<false><<<count, BLOCK, 0, st>>>(pos, items, ss, sr, n, eps2, 1.0, tk, fw, tb); }
-    } else if (s->dims3) {
-        const float eps2 = s->p.eps * s->p.eps;
-        const float4 *pos = (const float4 *)s->pos[s->cur];
-        float4 *ss = (float4 *)s->sym_slab_s, *sr = (float4 *)s->sym_slab_r;
-#define NB_SYM3_LAUNCH(RQ, UMB, PR, UMV) do { NB_TICKETS((force_sym3_f32<RQ, UMB, PR>)); force_sym3_f32<RQ, UMB, PR><<<count, BLOCK, 0, st>>>(pos, items, ss, sr, n, eps2, UMV, tk, fw, tb); } while (0)
-        // chunk pairs in 3-D pay with equal masses only (-1 ... -3 %); with individual masses the pair body needs 216 VGPRs
-        // (2 waves per SIMD) and loses 4 % (profiles/history/r03_chunk_pairs_3d.log): that case keeps the single-chunk sweep
-        // (any plan, even chunk counts included, runs on either kernel) unless nb_params.sym_chunk_pairs = 1 forces it
-        const bool pairs = s->sym_pairs && (s->uniform_mass || s->p.sym_chunk_pairs > 0);
-        if (s->uniform_mass) {
-            if (quake) { if (pairs) NB_SYM3_LAUNCH(RSQ_QUAKE, true, true, s->um_mass); else NB_SYM3_LAUNCH(RSQ_QUAKE, true, false, s->um_mass); }
-            else       { if (pairs) NB_SYM3_LAUNCH(RSQ_EXACT, true, true, s->um_mass); else NB_SYM3_LAUNCH(RSQ_EXACT, true, false, s->um_mass); }
-        } else {
-            if (quake) { if (pairs) NB_SYM3_LAUNCH(RSQ_QUAKE, false, true, 1.0f); else NB_SYM3_LAUNCH(RSQ_QUAKE, false, false, 1.0f); }
-            else       { if (pairs) NB_SYM3_LAUNCH(RSQ_EXACT, false, true, 1.0f); else NB_SYM3_LAUNCH(RSQ_EXACT, false, false, 1.0f); }
-        }
-#undef NB_SYM3_LAUNCH
-    } else if (s->fp64) {
-        const double eps2 = (double)s->p.eps * (double)s->p.eps;
-        const double2 *pos = (const double2 *)s->pos[s->cur];
-        const double *mass = (const double *)s->mass;
-        if (s->uniform_mass) { NB_TICKETS(force_sym_f64<true>);  force_sym_f64<true><<<count, BLOCK, 0, st>>>(pos, mass, items, (double2 *)s->sym_slab_s, (double2 *)s->sym_slab_r, n, eps2, (double)s->um_mass, tk, fw, tb); }
-        else                 { NB_TICKETS(force_sym_f64<false>); force_sym_f64<false><<<count, BLOCK, 0, st>>>(pos, mass, items, (double2 *)s->sym_slab_s, (double2 *)s->sym_slab_r, n, eps2, 1.0, tk, fw, tb); }
-    } else {
-        const float eps2 = s->p.eps * s->p.eps;
-        const float2 *pos = (const float2 *)s->pos[s->cur];
-        const float *mass = (const float *)s->mass;
-        float2 *ss = (float2 *)s->sym_slab_s, *sr = (float2 *)s->sym_slab_r;
-        const float *sg = s->sigma;
-#define NB_SYM_GO(KERNEL, UMV) do { NB_TICKETS(KERNEL); KERNEL<<<count, BLOCK, 0, st>>>(pos, mass, sg, items, ss, sr, n, eps2, UMV, tk, fw, tb); } while (0)
-#define NB_SYM_LAUNCH(RQ, MMODE, PR, UMV)                                                                                         \
-        do {                                                                                                                      \
-            if (s->sym_sb == SYM_SB_WS) NB_SYM_GO((force_sym_f32<RQ, MMODE, PR, true>), UMV);                                     \
-            else                        NB_SYM_GO((force_sym_f32<RQ, MMODE, PR, false>), UMV);                                    \
-        } while (0)
-        const bool pairs = s->sym_pairs && !s->mass_scaled;          // chunk pairs (sym_chunks2): large systems, see want_pairs
-        if (s->uniform_mass) {
-            if (quake) { if (pairs) NB_SYM_LAUNCH(RSQ_QUAKE, MM_UNIFORM, true, s->um_mass); else NB_SYM_LAUNCH(RSQ_QUAKE, MM_UNIFORM, false, s->um_mass); }
-            else       { if (pairs) NB_SYM_LAUNCH(RSQ_EXACT, MM_UNIFORM, true, s->um_mass); else NB_SYM_LAUNCH(RSQ_EXACT, MM_UNIFORM, false, s->um_mass); }
-        } else if (s->mass_scaled) {                 // exact rsqrt only (decided at upload)
-            NB_SYM_LAUNCH(RSQ_EXACT, MM_SCALED, false, 1.0f);
-        } else {
-            if (quake) { if (pairs) NB_SYM_LAUNCH(RSQ_QUAKE, MM_GENERAL, true, 1.0f); else NB_SYM_LAUNCH(RSQ_QUAKE, MM_GENERAL, false, 1.0f); }
-            else       { if (pairs) NB_SYM_LAUNCH(RSQ_EXACT, MM_GENERAL, true, 1.0f); else NB_SYM_LAUNCH(RSQ_EXACT, MM_GENERAL, false, 1.0f); }
-        }
-#undef NB_SYM_LAUNCH
-#undef NB_SYM_GO
-    }
-#undef NB_TICKETS
-    {
-        // The host's record of the tickets advances only with a launch that was accepted: if this one was refused, the device
-        // counter did not move either, but a kernel of an EARLIER launch may still be drawing — nothing sound can follow on
-        // this handle, so it is refused from here on (nb_step_begin) instead of indexing items[] with a base that may be off.
-        const hipError_t e_ = hipGetLastError();
-        if (e_ != hipSuccess) {
-            s->broken = true;
-            return nb_fail(hip_code(e_), "launch of the symmetric force kernel failed: %s; the handle is unusable from here on", hipGetErrorString(e_));
-        }
-        s->sym_ticket_base[slot] += drawn;
-    }
+    const uint32_t slot = first == 0 ? 0u : (first == s->sym_items_local ? 1u : 2u);   // the launch kind: told by where its items begin
+    const bool quake = s->p.rsqrt_mode == NB_RSQRT_QUAKE, um = s->uniform_mass, pairs = sym_uses_pairs(s);
+    const int rc = with_layout(s, [&](auto L) -> int {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        const real eps2 = (real)s->p.eps * (real)s->p.eps, umv = um ? (real)s->um_mass : (real)1;
+        const vec *pos = (const vec *)s->pos[s->cur];
+        vec *ss = (vec *)s->sym_slab_s, *sr = (vec *)s->sym_slab_r;
+        // the kernels' leading arguments differ by layout: (pos), (pos, mass) or (pos, mass, sigma)
+        auto go = [&](auto kernel, auto... lead) { return launch_sym_kernel(s, kernel, count, slot, st, lead..., items, ss, sr, n, eps2, umv); };
+        if constexpr (L.dims3 && std::is_same_v<real, double>)
+            return with_flags([&](auto u) { return go(force_sym3_f64<u>, pos); }, um);
+        else if constexpr (L.dims3)
+            return with_flags([&](auto q, auto u, auto pp) { return go(force_sym3_f32<q ? RSQ_QUAKE : RSQ_EXACT, u, pp>, pos); }, quake, um, pairs);
+        else if constexpr (std::is_same_v<real, double>)
+            return with_flags([&](auto u) { return go(force_sym_f64<u>, pos, (const double *)s->mass); }, um);
+        else
+            return with_flags([&](auto q, auto pp, auto ws) {
+                constexpr int RQ = q ? RSQ_QUAKE : RSQ_EXACT;
+                const float *mass = (const float *)s->mass;
+                if (um) return go(force_sym_f32<RQ, MM_UNIFORM, pp, ws>, pos, mass, s->sigma);
+                if constexpr (RQ == RSQ_EXACT && !pp)           // MM_SCALED: exact rsqrt only (decided at upload), no chunk pairs
+                    if (s->mass_scaled) return go(force_sym_f32<RSQ_EXACT, MM_SCALED, false, ws>, pos, mass, s->sigma);
+                return go(force_sym_f32<RQ, MM_GENERAL, pp, ws>, pos, mass, s->sigma);
+            }, quake, pairs, s->sym_sb == SYM_SB_WS);
+    });
+    if (rc) return rc;
     if (s->prof && prof_end(s, pr, st)) return NB_EHIP;
+    return NB_OK;
+}
+
+// One gather launch over particles [first, first + cnt): the slabs of rows [lo, hi) of every tile along the coverage lists
+// (cb, cov), plus `add` when given, stored to `dst` — or, fused, kick and drift applied in the same kernel.
+static int launch_gather(nb_sim *s, bool fuse, const uint32_t *lo, const uint32_t *hi, const uint32_t *cb, const SymCov *cov,
+                         uint32_t first, uint32_t cnt, void *dst, const void *add, double dt)
+{
+    const uint32_t n = (uint32_t)s->n, per = s->dims3 ? (uint32_t)GATHER_T : (uint32_t)GATHER_P, gg = (cnt + per - 1) / per;
+    const int extras = fuse ? s->p.extras : 0, kd = fuse ? INTEG_KICK | INTEG_DRIFT : 0;
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        const vec *ss = (const vec *)s->sym_slab_s, *sr = (const vec *)s->sym_slab_r;
+        const vec *pc = fuse ? (const vec *)s->pos[s->cur] : nullptr;
+        vec *pn = fuse ? (vec *)s->pos[s->cur ^ 1] : nullptr, *vel = fuse ? (vec *)s->vel : nullptr, *acc = fuse ? (vec *)s->acc : nullptr;
+        const real h = fuse ? (real)dt : (real)0;
+        with_flags([&](auto f) {
+            if constexpr (L.dims3)
+                sym_gather3<real, f><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, cov, n, first, cnt, (vec *)dst, (const vec *)add,
+                                                                  pc, pn, vel, acc, h, h, kd);
+            else
+                sym_gather<real, f><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, cov, n, first, cnt, (vec *)dst, (const vec *)add,
+                                                                 pc, pn, vel, acc, h, h, extras, kd, s->sym_sb_shift);
+        }, fuse);
+    });
+    HIPCHK(hipGetLastError());
     return NB_OK;
 }
 
@@ -1060,84 +1067,19 @@ static int launch_sym_items(nb_sim *s, uint32_t first, uint32_t count, hipStream
 // A sharded rank's late items are left out here (launch_sym_gather_late folds them in).
 static int launch_sym_gather(nb_sim *s, bool fuse_step, double dt)
 {
-    const uint32_t n = (uint32_t)s->n, per = s->dims3 ? (uint32_t)GATHER_T : (uint32_t)GATHER_P, gg = (n + per - 1) / per, tiles = s->sym_tiles;
-    void *dst = (s->sym_sharded || s->sym_replicated) ? s->acc_full : s->partial;
-    const uint32_t *lo = s->sym_rowbase_dev, *hi = s->sym_rowbase_dev + tiles;      // [first row, first late row)
-    const uint32_t *cb = s->sym_cov_begin_dev;                                      // coverage lists of the main gather
-    const int nxt = s->cur ^ 1, kd = INTEG_KICK | INTEG_DRIFT;
-    if (s->dims3 && s->fp64) {
-        const double4 *ss = (const double4 *)s->sym_slab_s, *sr = (const double4 *)s->sym_slab_r;
-        if (fuse_step)
-            sym_gather3<double, true><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, s->sym_cov_dev, n, 0u, n, (double4 *)dst, nullptr,
-                                                                   (const double4 *)s->pos[s->cur], (double4 *)s->pos[nxt], (double4 *)s->vel, (double4 *)s->acc,
-                                                                   dt, dt, kd);
-        else
-            sym_gather3<double, false><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, s->sym_cov_dev, n, 0u, n, (double4 *)dst, nullptr,
-                                                                    nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, 0);
-    } else if (s->dims3) {
-        const float4 *ss = (const float4 *)s->sym_slab_s, *sr = (const float4 *)s->sym_slab_r;
-        if (fuse_step)
-            sym_gather3<float, true><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, s->sym_cov_dev, n, 0u, n, (float4 *)dst, nullptr,
-                                                                  (const float4 *)s->pos[s->cur], (float4 *)s->pos[nxt], (float4 *)s->vel, (float4 *)s->acc,
-                                                                  (float)dt, (float)dt, kd);
-        else
-            sym_gather3<float, false><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, s->sym_cov_dev, n, 0u, n, (float4 *)dst, nullptr,
-                                                                   nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0);
-    } else if (s->fp64) {
-        const double2 *ss = (const double2 *)s->sym_slab_s, *sr = (const double2 *)s->sym_slab_r;
-        if (fuse_step)
-            sym_gather<double, true><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, s->sym_cov_dev, n, 0u, n, (double2 *)dst, nullptr,
-                                                                  (const double2 *)s->pos[s->cur], (double2 *)s->pos[nxt], (double2 *)s->vel, (double2 *)s->acc,
-                                                                  dt, dt, s->p.extras, kd, s->sym_sb_shift);
-        else
-            sym_gather<double, false><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, s->sym_cov_dev, n, 0u, n, (double2 *)dst, nullptr,
-                                                                   nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, 0, 0, s->sym_sb_shift);
-    } else {
-        const float2 *ss = (const float2 *)s->sym_slab_s, *sr = (const float2 *)s->sym_slab_r;
-        if (fuse_step)
-            sym_gather<float, true><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, s->sym_cov_dev, n, 0u, n, (float2 *)dst, nullptr,
-                                                                 (const float2 *)s->pos[s->cur], (float2 *)s->pos[nxt], (float2 *)s->vel, (float2 *)s->acc,
-                                                                 (float)dt, (float)dt, s->p.extras, kd, s->sym_sb_shift);
-        else
-            sym_gather<float, false><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, s->sym_cov_dev, n, 0u, n, (float2 *)dst, nullptr,
-                                                                  nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0, 0, s->sym_sb_shift);
-    }
-    HIPCHK(hipGetLastError());
-    return NB_OK;
+    void *dst = s->path == StepPath::SYM ? s->partial : s->acc_full;
+    return launch_gather(s, fuse_step, s->sym_rowbase_dev, s->sym_rowbase_dev + s->sym_tiles,     // [first row, first late row)
+                         s->sym_cov_begin_dev, s->sym_cov_dev, 0u, (uint32_t)s->n, dst, nullptr, dt);
 }
 
 // Sharded rank, after the reduce-scatter: acceleration of the owned block = acc_owned (the summed partials of all
 // ranks) + the slabs of this rank's late items; kick and drift applied in the same kernel.
 static int launch_sym_gather_late(nb_sim *s, double dt)
 {
-    const uint32_t n = (uint32_t)s->n, ic = (uint32_t)s->i_count, ib = (uint32_t)s->i_begin;
-    const uint32_t per = s->dims3 ? (uint32_t)GATHER_T : (uint32_t)GATHER_P, gg = (ic + per - 1) / per, tiles = s->sym_tiles;
-    const uint32_t *lo = s->sym_rowbase_dev + tiles, *hi = s->sym_rowbase_dev + 2 * (size_t)tiles;   // [first late row, end row)
-    const uint32_t *cb = s->sym_cov_begin_dev + (tiles + 1);                        // coverage lists of the late segments
-    const SymCov *cov = s->sym_cov_dev + s->sym_cov_late_off;
-    const int nxt = s->cur ^ 1, kd = INTEG_KICK | INTEG_DRIFT;
-    if (s->dims3 && s->fp64)
-        sym_gather3<double, true><<<gg, BLOCK, 0, s->stream>>>((const double4 *)s->sym_slab_s, (const double4 *)s->sym_slab_r, lo, hi, cb, cov,
-                                                               n, ib, ic, nullptr, (const double4 *)s->acc_owned,
-                                                               (const double4 *)s->pos[s->cur], (double4 *)s->pos[nxt], (double4 *)s->vel, (double4 *)s->acc,
-                                                               dt, dt, kd);
-    else if (s->dims3)
-        sym_gather3<float, true><<<gg, BLOCK, 0, s->stream>>>((const float4 *)s->sym_slab_s, (const float4 *)s->sym_slab_r, lo, hi, cb, cov,
-                                                              n, ib, ic, nullptr, (const float4 *)s->acc_owned,
-                                                              (const float4 *)s->pos[s->cur], (float4 *)s->pos[nxt], (float4 *)s->vel, (float4 *)s->acc,
-                                                              (float)dt, (float)dt, kd);
-    else if (s->fp64)
-        sym_gather<double, true><<<gg, BLOCK, 0, s->stream>>>((const double2 *)s->sym_slab_s, (const double2 *)s->sym_slab_r, lo, hi, cb, cov,
-                                                              n, ib, ic, nullptr, (const double2 *)s->acc_owned,
-                                                              (const double2 *)s->pos[s->cur], (double2 *)s->pos[nxt], (double2 *)s->vel, (double2 *)s->acc,
-                                                              dt, dt, s->p.extras, kd, s->sym_sb_shift);
-    else
-        sym_gather<float, true><<<gg, BLOCK, 0, s->stream>>>((const float2 *)s->sym_slab_s, (const float2 *)s->sym_slab_r, lo, hi, cb, cov,
-                                                             n, ib, ic, nullptr, (const float2 *)s->acc_owned,
-                                                             (const float2 *)s->pos[s->cur], (float2 *)s->pos[nxt], (float2 *)s->vel, (float2 *)s->acc,
-                                                             (float)dt, (float)dt, s->p.extras, kd, s->sym_sb_shift);
-    HIPCHK(hipGetLastError());
-    return NB_OK;
+    const uint32_t tiles = s->sym_tiles;
+    return launch_gather(s, true, s->sym_rowbase_dev + tiles, s->sym_rowbase_dev + 2 * (size_t)tiles,   // [first late row, end row)
+                         s->sym_cov_begin_dev + (tiles + 1), s->sym_cov_dev + s->sym_cov_late_off,      // coverage lists of the late segments
+                         (uint32_t)s->i_begin, (uint32_t)s->i_count, nullptr, s->acc_owned, dt);
 }
 
 // Whole-system symmetric force (+ optionally the kick/drift).
@@ -1151,124 +1093,110 @@ static int launch_force_sym(nb_sim *s, bool fuse_step = false, double dt = 0.0)
 static int launch_force(nb_sim *s, const ForceJob &j)
 {
     if (j.j_end <= j.j_begin || j.js == 0) return NB_OK;
-    if (s->sym && &j == &s->job_all) return launch_force_sym(s);
+    if (s->path == StepPath::SYM && &j == &s->job_all) return launch_force_sym(s);
     std::pair<hipEvent_t, hipEvent_t> pr;
     if (s->prof && prof_begin(s, &pr)) return NB_EHIP;
-    const bool guard = needs_guard(s);
-    const uint32_t ic = (uint32_t)s->i_count;
-    if (s->dims3 && s->fp64) {
-        const double eps2 = (double)s->p.eps * (double)s->p.eps;
-        const uint32_t grid = grid_blocks(j.i_tiles, j.js);
-        double4 *out = (double4 *)s->partial + (size_t)j.slab0 * s->i_count;
-        const double4 *pos = (const double4 *)s->pos[s->cur];
-#define NB_LAUNCH3D(PP, GD)                                                                                            \
-        force_tiled3_f64<PP, GD, 4><<<grid, BLOCK, 0, s->stream>>>(pos, out, (uint32_t)s->i_begin, ic, j.j_begin, j.j_end, j.js, j.i_tiles, \
-                                                                   eps2, j.gap_begin, j.gap_len)
-        if (j.P == 2) { if (guard) NB_LAUNCH3D(2, true); else NB_LAUNCH3D(2, false); }
-        else          { if (guard) NB_LAUNCH3D(1, true); else NB_LAUNCH3D(1, false); }
-#undef NB_LAUNCH3D
-        HIPCHK(hipGetLastError());
-        if (s->prof && prof_end(s, pr)) return NB_EHIP;
-        return NB_OK;
-    }
-    if (s->dims3) {
-        const float eps2 = s->p.eps * s->p.eps;
-        const uint32_t grid = grid_blocks(j.i_tiles, j.js);
-        float4 *out = (float4 *)s->partial + (size_t)j.slab0 * s->i_count;
-        const float4 *pos = (const float4 *)s->pos[s->cur];
-        const bool quake = s->p.rsqrt_mode == NB_RSQRT_QUAKE, um = s->uniform_mass && !guard;
-#define NB_LAUNCH3(PP, RQ, GD, UMM)                                                                                   \
-        force_tiled3_f32<PP, RQ, GD, 8, UMM><<<grid, BLOCK, 0, s->stream>>>(pos, out, (uint32_t)s->i_begin, ic, j.j_begin, j.j_end, \
-                                                                            j.js, j.i_tiles, eps2, um ? s->um_mass : 1.0f, j.gap_begin, j.gap_len)
-#define NB_DISPATCH3(PP)                                                                                              \
-        do {                                                                                                          \
-            if (guard)      { if (quake) NB_LAUNCH3(PP, RSQ_QUAKE, true, false); else NB_LAUNCH3(PP, RSQ_EXACT, true, false); }   \
-            else if (um)    { if (quake) NB_LAUNCH3(PP, RSQ_QUAKE, false, true); else NB_LAUNCH3(PP, RSQ_EXACT, false, true); }   \
-            else            { if (quake) NB_LAUNCH3(PP, RSQ_QUAKE, false, false); else NB_LAUNCH3(PP, RSQ_EXACT, false, false); } \
-        } while (0)
-        if (j.P == 4) NB_DISPATCH3(4); else if (j.P == 2) NB_DISPATCH3(2); else NB_DISPATCH3(1);
-#undef NB_DISPATCH3
-#undef NB_LAUNCH3
-        HIPCHK(hipGetLastError());
-        if (s->prof && prof_end(s, pr)) return NB_EHIP;
-        return NB_OK;
-    }
-    if (s->fp64) {
-        const double eps2 = (double)s->p.eps * (double)s->p.eps;
-        if (j.P == 2) { if (guard) launch_tiled_f64<2, true>(s, j, eps2); else launch_tiled_f64<2, false>(s, j, eps2); }
-        else          { if (guard) launch_tiled_f64<1, true>(s, j, eps2); else launch_tiled_f64<1, false>(s, j, eps2); }
-    } else {
-        const float eps2 = s->p.eps * s->p.eps;   // Quadtree.hpp:19  e_sq(epsilon * epsilon)
-        if (s->p.sum_order == NB_SUM_SEQUENTIAL) {
-            const uint32_t grid = (ic + BLOCK - 1) / BLOCK;
-            float2 *out = (float2 *)s->partial + (size_t)j.slab0 * s->i_count;
-            if (s->p.rsqrt_mode == NB_RSQRT_QUAKE)
-                force_seq_f32<RSQ_QUAKE><<<grid, BLOCK, 0, s->stream>>>((const float2 *)s->pos[s->cur], (const float *)s->mass, out,
-                                                                          (uint32_t)s->i_begin, ic, j.j_begin, j.j_end, eps2);
-            else
-                force_seq_f32<RSQ_EXACT><<<grid, BLOCK, 0, s->stream>>>((const float2 *)s->pos[s->cur], (const float *)s->mass, out,
-                                                                          (uint32_t)s->i_begin, ic, j.j_begin, j.j_end, eps2);
+    const bool guard = needs_guard(s), quake = s->p.rsqrt_mode == NB_RSQRT_QUAKE;
+    // the hoisted-mass and mass-scaled bodies have no guard form; mass_scaled implies exact rsqrt (decided at upload)
+    const bool um = s->uniform_mass && !guard, scaled = s->mass_scaled && !guard;
+    const uint32_t ib = (uint32_t)s->i_begin, ic = (uint32_t)s->i_count, grid = grid_blocks(j.i_tiles, j.js);
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        const real eps2 = (real)s->p.eps * (real)s->p.eps;   // Quadtree.hpp:19  e_sq(epsilon * epsilon)
+        const vec *pos = (const vec *)s->pos[s->cur];
+        vec *out = (vec *)s->partial + (size_t)j.slab0 * s->i_count;
+        if constexpr (std::is_same_v<real, double>) {
+            with_lanes<2>(j.P, [&](auto P) { with_flags([&](auto g) {
+                if constexpr (L.dims3)
+                    force_tiled3_f64<P, g, 4><<<grid, BLOCK, 0, s->stream>>>(pos, out, ib, ic, j.j_begin, j.j_end, j.js, j.i_tiles, eps2,
+                                                                             j.gap_begin, j.gap_len);
+                else
+                    force_tiled_f64<P, g, 4><<<grid, BLOCK, 0, s->stream>>>(pos, (const double *)s->mass, out, ib, ic, j.j_begin, j.j_end,
+                                                                            j.js, j.i_tiles, eps2, j.gap_begin, j.gap_len);
+            }, guard); });
+        } else if constexpr (L.dims3) {
+            with_lanes<4>(j.P, [&](auto P) { with_flags([&](auto q, auto g) {
+                constexpr int RQ = q ? RSQ_QUAKE : RSQ_EXACT;
+                auto go = [&](auto kernel, float umv) {
+                    kernel<<<grid, BLOCK, 0, s->stream>>>(pos, out, ib, ic, j.j_begin, j.j_end, j.js, j.i_tiles, eps2, umv, j.gap_begin, j.gap_len);
+                };
+                if constexpr (!g)
+                    if (um) return go(force_tiled3_f32<P, RQ, false, 8, true>, s->um_mass);
+                go(force_tiled3_f32<P, RQ, g, 8, false>, 1.0f);
+            }, quake, guard); });
+        } else if (s->p.sum_order == NB_SUM_SEQUENTIAL) {
+            with_flags([&](auto q) {
+                force_seq_f32<q ? RSQ_QUAKE : RSQ_EXACT><<<(ic + BLOCK - 1) / BLOCK, BLOCK, 0, s->stream>>>(
+                    pos, (const float *)s->mass, out, ib, ic, j.j_begin, j.j_end, eps2);
+            }, quake);
         } else {
-            const bool quake = s->p.rsqrt_mode == NB_RSQRT_QUAKE;
-#define NB_DISPATCH(PP)                                                                           \
-            do {                                                                                  \
-                if (quake) { if (guard) launch_tiled_f32<PP, RSQ_QUAKE, true>(s, j, eps2);  \
-                             else       launch_tiled_f32<PP, RSQ_QUAKE, false>(s, j, eps2); } \
-                else       { if (guard) launch_tiled_f32<PP, RSQ_EXACT, true>(s, j, eps2);  \
-                             else       launch_tiled_f32<PP, RSQ_EXACT, false>(s, j, eps2); } \
-            } while (0)
-            if (j.P == 4) NB_DISPATCH(4); else if (j.P == 2) NB_DISPATCH(2); else NB_DISPATCH(1);
-#undef NB_DISPATCH
+            with_lanes<4>(j.P, [&](auto P) { with_flags([&](auto q, auto g) {
+                constexpr int RQ = q ? RSQ_QUAKE : RSQ_EXACT;
+                auto go = [&](auto kernel, float umv) {
+                    kernel<<<grid, BLOCK, 0, s->stream>>>(pos, (const float *)s->mass, s->sigma, out, ib, ic, j.j_begin, j.j_end, j.js,
+                                                          j.i_tiles, eps2, umv, j.gap_begin, j.gap_len);
+                };
+                if constexpr (!g) {
+                    if (um) return go(force_tiled_f32<P, RQ, false, 8, true, F32_WS>, s->um_mass);
+                    if constexpr (RQ == RSQ_EXACT)     // individual masses folded into the pair geometry: no mass multiply in the body
+                        if (scaled) return go(force_tiled_f32<P, RSQ_EXACT, false, 8, false, F32_WS, true>, 1.0f);
+                }
+                go(force_tiled_f32<P, RQ, g, 8, false, F32_WS>, 1.0f);
+            }, quake, guard); });
         }
-    }
+    });
     HIPCHK(hipGetLastError());
     if (s->prof && prof_end(s, pr)) return NB_EHIP;
     return NB_OK;
 }
 
-static int launch_integrate(nb_sim *s, uint32_t nslabs, double dt_kick, double dt_drift, int flags)
+// Kick and drift (as `flags` ask) of particles [first, first + cnt) with the sum of `nslabs` slabs of `src` as their
+// acceleration: the one-sided kernels' partials, or the one summed slab of a sharded or replicated handle's exchange.
+static int launch_integrate(nb_sim *s, const void *src, uint32_t nslabs, uint32_t first, uint32_t cnt, double dt_kick, double dt_drift, int flags)
 {
-    const uint32_t ic = (uint32_t)s->i_count, g = (ic + BLOCK - 1) / BLOCK;
+    const uint32_t g = (cnt + BLOCK - 1) / BLOCK;
     const bool strict = s->p.sum_order == NB_SUM_SEQUENTIAL;
-    const int nxt = s->cur ^ 1;
-    if (s->dims3 && s->fp64)
-        integrate3<double><<<g, BLOCK, 0, s->stream>>>((const double4 *)s->pos[s->cur], (double4 *)s->pos[nxt], (double4 *)s->vel, (double4 *)s->acc,
-                                                       (const double4 *)s->partial, nslabs, (uint32_t)s->i_begin, ic, dt_kick, dt_drift, flags);
-    else if (s->dims3)
-        integrate3<float><<<g, BLOCK, 0, s->stream>>>((const float4 *)s->pos[s->cur], (float4 *)s->pos[nxt], (float4 *)s->vel, (float4 *)s->acc,
-                                                      (const float4 *)s->partial, nslabs, (uint32_t)s->i_begin, ic, (float)dt_kick, (float)dt_drift, flags);
-    else if (s->fp64)
-        integrate<double, false><<<g, BLOCK, 0, s->stream>>>((const double2 *)s->pos[s->cur], (double2 *)s->pos[nxt], (double2 *)s->vel,
-                                                             (double2 *)s->acc, (const double2 *)s->partial, nslabs,
-                                                             (uint32_t)s->i_begin, ic, dt_kick, dt_drift, s->p.extras, flags);
-    else if (strict)
-        integrate<float, true><<<g, BLOCK, 0, s->stream>>>((const float2 *)s->pos[s->cur], (float2 *)s->pos[nxt], (float2 *)s->vel,
-                                                           (float2 *)s->acc, (const float2 *)s->partial, nslabs,
-                                                           (uint32_t)s->i_begin, ic, (float)dt_kick, (float)dt_drift, s->p.extras, flags);
-    else
-        integrate<float, false><<<g, BLOCK, 0, s->stream>>>((const float2 *)s->pos[s->cur], (float2 *)s->pos[nxt], (float2 *)s->vel,
-                                                            (float2 *)s->acc, (const float2 *)s->partial, nslabs,
-                                                            (uint32_t)s->i_begin, ic, (float)dt_kick, (float)dt_drift, s->p.extras, flags);
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        const vec *pc = (const vec *)s->pos[s->cur], *sl = (const vec *)src;
+        vec *pn = (vec *)s->pos[s->cur ^ 1], *vel = (vec *)s->vel, *acc = (vec *)s->acc;
+        if constexpr (L.dims3) {
+            integrate3<real><<<g, BLOCK, 0, s->stream>>>(pc, pn, vel, acc, sl, nslabs, first, cnt, (real)dt_kick, (real)dt_drift, flags);
+        } else {
+            auto go = [&](auto kernel) {
+                kernel<<<g, BLOCK, 0, s->stream>>>(pc, pn, vel, acc, sl, nslabs, first, cnt, (real)dt_kick, (real)dt_drift, s->p.extras, flags);
+            };
+            if constexpr (std::is_same_v<real, float>)
+                if (strict) return go(integrate<float, true>);      // the sequential order's strict form: fp32 2-D only
+            go(integrate<real, false>);
+        }
+    });
     HIPCHK(hipGetLastError());
     return NB_OK;
+}
+
+// The one-sided form: the force partials of the owned block.
+static int integrate_slabs(nb_sim *s, uint32_t nslabs, double dt_kick, double dt_drift, int flags)
+{
+    return launch_integrate(s, s->partial, nslabs, (uint32_t)s->i_begin, (uint32_t)s->i_count, dt_kick, dt_drift, flags);
 }
 
 // ---------------------------------------------------------------------------
 // stepping
 // ---------------------------------------------------------------------------
-static bool sharded(const nb_sim *s) { return s->i_count != s->n; }
-static bool two_phase(const nb_sim *s) { return sharded(s) && s->p.sum_order != NB_SUM_SEQUENTIAL && !s->sym_sharded; }
-
 static int step_begin_enqueue(nb_sim *s)
 {
-    if (s->sym_replicated) {
+    switch (s->path) {
+    case StepPath::SYM_REPLICATED: {
         // every position is already here (each rank integrates everything): all items in one launch, then this rank's
         // PARTIAL acceleration of every particle -> acc_full, which the host all-reduces before nb_step_finish
         int rc = launch_sym_items(s, 0, s->sym_items);
         if (rc) return rc;
         return launch_sym_gather(s, false, 0.0);
     }
-    if (s->sym_sharded) {
+    case StepPath::SYM_SHARDED: {
         // pairs inside my own block: no remote data needed.  On the side stream (ordered after everything
         // enqueued so far), so the cross items of nb_step_mid fill the CUs its last workgroups leave idle.
         if (!s->aux_local) return launch_sym_items(s, 0, s->sym_items_local);
@@ -1279,8 +1207,13 @@ static int step_begin_enqueue(nb_sim *s)
         HIPCHK(hipEventRecord(s->ev_join, s->aux));
         return NB_OK;
     }
-    // local j-block first: its positions are already resident, so this overlaps the exchange
-    if (two_phase(s)) return launch_force(s, s->job_local);
+    case StepPath::TWO_PHASE:
+        // local j-block first: its positions are already resident, so this overlaps the exchange
+        return launch_force(s, s->job_local);
+    case StepPath::SYM:
+    case StepPath::ONE_SIDED:
+        break;
+    }
     return NB_OK;
 }
 
@@ -1302,7 +1235,7 @@ extern "C" int nb_step_mid(nb_sim *s)
 {
     if (!s) return nb_fail(NB_EINVAL, "nb_step_mid: NULL handle");
     if (!s->in_step) return nb_fail(NB_ESTATE, "nb_step_mid: no step in flight");
-    if (!s->sym_sharded) return NB_OK;                 // nothing between begin and finish in the other protocols
+    if (s->path != StepPath::SYM_SHARDED) return NB_OK;   // nothing between begin and finish in the other protocols
     if (s->mid_done) return nb_fail(NB_ESTATE, "nb_step_mid: already called for this step");
     if (bind(s)) return NB_EHIP;
     int rc = launch_sym_items(s, s->sym_items_local, s->sym_items_cross);   // cross-block pairs: need the gathered positions
@@ -1327,80 +1260,35 @@ extern "C" int nb_step_finish(nb_sim *s)
     if (!s->in_step) return nb_fail(NB_ESTATE, "nb_step_finish: no step in flight");
     if (bind(s)) return NB_EHIP;
     s->in_step = false;
+    const double dt = s->pending_dt;
     int rc;
-    uint32_t nslabs;
-    if (s->sym_replicated) {
+    switch (s->path) {
+    case StepPath::SYM_REPLICATED:
         // acc_full holds the all-reduced acceleration of every particle: kick and drift them all
-        const uint32_t nn = (uint32_t)s->n, g = (nn + BLOCK - 1) / BLOCK;
-        const int nxt = s->cur ^ 1;
-        const float dt = s->pending_dt;
-        if (s->dims3 && s->fp64)
-            integrate3<double><<<g, BLOCK, 0, s->stream>>>((const double4 *)s->pos[s->cur], (double4 *)s->pos[nxt], (double4 *)s->vel, (double4 *)s->acc,
-                                                           (const double4 *)s->acc_full, 1u, 0u, nn, (double)dt, (double)dt, INTEG_KICK | INTEG_DRIFT);
-        else if (s->dims3)
-            integrate3<float><<<g, BLOCK, 0, s->stream>>>((const float4 *)s->pos[s->cur], (float4 *)s->pos[nxt], (float4 *)s->vel, (float4 *)s->acc,
-                                                          (const float4 *)s->acc_full, 1u, 0u, nn, dt, dt, INTEG_KICK | INTEG_DRIFT);
-        else if (s->fp64)
-            integrate<double, false><<<g, BLOCK, 0, s->stream>>>((const double2 *)s->pos[s->cur], (double2 *)s->pos[nxt], (double2 *)s->vel,
-                                                                 (double2 *)s->acc, (const double2 *)s->acc_full, 1u, 0u, nn,
-                                                                 (double)dt, (double)dt, s->p.extras, INTEG_KICK | INTEG_DRIFT);
-        else
-            integrate<float, false><<<g, BLOCK, 0, s->stream>>>((const float2 *)s->pos[s->cur], (float2 *)s->pos[nxt], (float2 *)s->vel,
-                                                                (float2 *)s->acc, (const float2 *)s->acc_full, 1u, 0u, nn, dt, dt,
-                                                                s->p.extras, INTEG_KICK | INTEG_DRIFT);
-        HIPCHK(hipGetLastError());
-        s->cur ^= 1;
-        s->frame += 1;
-        s->acc_valid = false;
-        return NB_OK;
-    }
-    if (s->sym_sharded) {
+        if ((rc = launch_integrate(s, s->acc_full, 1, 0u, (uint32_t)s->n, dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc;
+        break;
+    case StepPath::SYM_SHARDED:
         if (!s->mid_done) { s->in_step = true; return nb_fail(NB_ESTATE, "nb_step_finish: symmetric sharded handle needs nb_step_mid (and the reduce-scatter) first"); }
         s->mid_done = false;
         // the host has reduce-scattered acc_full into acc_owned: it is the one slab of the owned block
-        const uint32_t ic = (uint32_t)s->i_count, g = (ic + BLOCK - 1) / BLOCK;
-        const int nxt = s->cur ^ 1;
-        const float dt = s->pending_dt;
         if (s->sym_items_late) {
             HIPCHK(hipStreamWaitEvent(s->stream, s->ev_late, 0));
-            if ((rc = launch_sym_gather_late(s, (double)dt))) return rc;
-        } else if (s->dims3 && s->fp64)
-            integrate3<double><<<g, BLOCK, 0, s->stream>>>((const double4 *)s->pos[s->cur], (double4 *)s->pos[nxt], (double4 *)s->vel, (double4 *)s->acc,
-                                                           (const double4 *)s->acc_owned, 1u, (uint32_t)s->i_begin, ic, (double)dt, (double)dt,
-                                                           INTEG_KICK | INTEG_DRIFT);
-        else if (s->dims3)
-            integrate3<float><<<g, BLOCK, 0, s->stream>>>((const float4 *)s->pos[s->cur], (float4 *)s->pos[nxt], (float4 *)s->vel, (float4 *)s->acc,
-                                                          (const float4 *)s->acc_owned, 1u, (uint32_t)s->i_begin, ic, dt, dt, INTEG_KICK | INTEG_DRIFT);
-        else if (s->fp64)
-            integrate<double, false><<<g, BLOCK, 0, s->stream>>>((const double2 *)s->pos[s->cur], (double2 *)s->pos[nxt], (double2 *)s->vel,
-                                                                 (double2 *)s->acc, (const double2 *)s->acc_owned, 1u, (uint32_t)s->i_begin, ic,
-                                                                 (double)dt, (double)dt, s->p.extras, INTEG_KICK | INTEG_DRIFT);
-        else
-            integrate<float, false><<<g, BLOCK, 0, s->stream>>>((const float2 *)s->pos[s->cur], (float2 *)s->pos[nxt], (float2 *)s->vel,
-                                                                (float2 *)s->acc, (const float2 *)s->acc_owned, 1u, (uint32_t)s->i_begin, ic, dt, dt,
-                                                                s->p.extras, INTEG_KICK | INTEG_DRIFT);
-        HIPCHK(hipGetLastError());
-        s->cur ^= 1;
-        s->frame += 1;
-        return NB_OK;
-    }
-    if (s->sym && s->p.integrator == NB_INTEGRATOR_KICK_DRIFT) {
+            if ((rc = launch_sym_gather_late(s, dt))) return rc;
+        } else if ((rc = launch_integrate(s, s->acc_owned, 1, (uint32_t)s->i_begin, (uint32_t)s->i_count, dt, dt, INTEG_KICK | INTEG_DRIFT))) {
+            return rc;
+        }
+        break;
+    case StepPath::SYM:
         // whole system, symmetric kernel: the gather launch applies the kick and the drift itself
-        if ((rc = launch_force_sym(s, true, (double)s->pending_dt))) return rc;
-        s->cur ^= 1;
-        s->frame += 1;
-        s->acc_valid = false;
-        return NB_OK;
+        if ((rc = launch_force_sym(s, true, dt))) return rc;
+        break;
+    case StepPath::TWO_PHASE:
+        if ((rc = launch_force(s, s->job_remote)) || (rc = integrate_slabs(s, s->slabs_two_phase, dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc;
+        break;
+    case StepPath::ONE_SIDED:
+        if ((rc = launch_force(s, s->job_all)) || (rc = integrate_slabs(s, s->slabs_all, dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc;
+        break;
     }
-    if (two_phase(s)) {
-        if ((rc = launch_force(s, s->job_remote))) return rc;
-        nslabs = s->slabs_two_phase;
-    } else {
-        if ((rc = launch_force(s, s->job_all))) return rc;
-        nslabs = s->slabs_all;
-    }
-    const double dt = s->pending_dt;
-    if ((rc = launch_integrate(s, nslabs, dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc;
     s->cur ^= 1;
     s->frame += 1;                                  // Simulation.hpp:74
     s->acc_valid = false;
@@ -1412,16 +1300,16 @@ static int step_kdk(nb_sim *s, double dt)
     int rc;
     if (!s->acc_valid) {                            // a(x_n), first step only
         if ((rc = launch_force(s, s->job_all))) return rc;
-        if ((rc = launch_integrate(s, s->slabs_all, 0.0, 0.0, 0))) return rc;   // acc <- slabs only
+        if ((rc = integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0))) return rc;   // acc <- slabs only
     } else {
         // acc already holds a(x_n): re-present it as the single slab 0
         HIPCHK(hipMemcpyAsync(s->partial, s->acc, s->i_count * s->esz, hipMemcpyDeviceToDevice, s->stream));
     }
     // half kick + drift (acc from slab(s)), then force at x_{n+1} and the second half kick
-    if ((rc = launch_integrate(s, s->acc_valid ? 1 : s->slabs_all, 0.5 * dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc;
+    if ((rc = integrate_slabs(s, s->acc_valid ? 1 : s->slabs_all, 0.5 * dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc;
     s->cur ^= 1;
     if ((rc = launch_force(s, s->job_all))) return rc;
-    if ((rc = launch_integrate(s, s->slabs_all, 0.5 * dt, 0.0, INTEG_KICK))) return rc;
+    if ((rc = integrate_slabs(s, s->slabs_all, 0.5 * dt, 0.0, INTEG_KICK))) return rc;
     s->acc_valid = true;
     s->frame += 1;
     return NB_OK;
@@ -1431,7 +1319,7 @@ extern "C" int nb_step(nb_sim *s, float dt, int nsteps)
 {
     if (!s) return nb_fail(NB_EINVAL, "nb_step: NULL handle");
     if (nsteps < 0) return nb_fail(NB_EINVAL, "nb_step: nsteps < 0");
-    if (sharded(s) || s->sym_replicated || s->sym_sharded) return nb_fail(NB_ESTATE, "nb_step: sharded handle — drive it with nb_step_begin / exchange / nb_step_finish");
+    if (s->i_count != s->n || s->path == StepPath::SYM_REPLICATED || s->path == StepPath::SYM_SHARDED) return nb_fail(NB_ESTATE, "nb_step: sharded handle — drive it with nb_step_begin / exchange / nb_step_finish");
     if (s->in_step) return nb_fail(NB_ESTATE, "nb_step: a split step is in flight");
     if (bind(s)) return NB_EHIP;
     const float h = dt > 0.0f ? dt : s->p.dt;
@@ -1452,8 +1340,9 @@ extern "C" int nb_accelerations(nb_sim *s)
     if (s->in_step) return nb_fail(NB_ESTATE, "nb_accelerations: a split step is in flight");
     if (bind(s)) return NB_EHIP;
     int rc;
+    // job_all: a sharded or replicated handle has no whole-system plan, so this takes the one-sided kernels
     if ((rc = launch_force(s, s->job_all))) return rc;
-    return launch_integrate(s, s->slabs_all, 0.0, 0.0, 0);   // acc <- sum of slabs, nothing else
+    return integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0);   // acc <- sum of slabs, nothing else
 }
 
 extern "C" int nb_wait(nb_sim *s)
@@ -1545,16 +1434,15 @@ static int launch_pack_range(nb_sim *s, BodyRec *out, uint32_t o, uint32_t cnt)
     const uint32_t g = (cnt + BLOCK - 1) / BLOCK, ib = (uint32_t)s->i_begin + o;
     const size_t e = s->esz * (size_t)o;                 // vel / acc are indexed from the start of the owned block
     const char *vel = (const char *)s->vel + e, *acc = (const char *)s->acc + e;
-    if (s->dims3 && s->fp64)
-        pack_bodies3<double><<<g, BLOCK, 0, s->stream>>>(out, (const double4 *)s->pos[s->cur], (const double4 *)vel, (const double4 *)acc, s->radius, ib, cnt);
-    else if (s->dims3)
-        pack_bodies3<float><<<g, BLOCK, 0, s->stream>>>(out, (const float4 *)s->pos[s->cur], (const float4 *)vel, (const float4 *)acc, s->radius, ib, cnt);
-    else if (s->fp64)
-        pack_bodies<double><<<g, BLOCK, 0, s->stream>>>(out, (const double2 *)s->pos[s->cur], (const double *)s->mass,
-                                                        (const double2 *)vel, (const double2 *)acc, s->radius, ib, cnt);
-    else
-        pack_bodies<float><<<g, BLOCK, 0, s->stream>>>(out, (const float2 *)s->pos[s->cur], (const float *)s->mass,
-                                                       (const float2 *)vel, (const float2 *)acc, s->radius, ib, cnt);
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        const vec *pos = (const vec *)s->pos[s->cur];
+        if constexpr (L.dims3)
+            pack_bodies3<real><<<g, BLOCK, 0, s->stream>>>(out, pos, (const vec *)vel, (const vec *)acc, s->radius, ib, cnt);
+        else
+            pack_bodies<real><<<g, BLOCK, 0, s->stream>>>(out, pos, (const real *)s->mass, (const vec *)vel, (const vec *)acc, s->radius, ib, cnt);
+    });
     HIPCHK(hipGetLastError());
     return NB_OK;
 }
@@ -1641,16 +1529,18 @@ extern "C" int nb_sync_positions(nb_sim *s, float *out_xy)
     const uint32_t ic = (uint32_t)s->i_count, g = (ic + BLOCK - 1) / BLOCK;
     const size_t bytes = s->i_count * (s->dims3 ? 3 : 2) * sizeof(float);       // (x, y) or (x, y, z) per body
     const void *src = s->aos_dev;
-    if (s->dims3) {
-        if (s->fp64) pack_positions3<double><<<g, BLOCK, 0, s->stream>>>((float *)s->aos_dev, (const double4 *)s->pos[s->cur], (uint32_t)s->i_begin, ic);
-        else         pack_positions3<float><<<g, BLOCK, 0, s->stream>>>((float *)s->aos_dev, (const float4 *)s->pos[s->cur], (uint32_t)s->i_begin, ic);
-        HIPCHK(hipGetLastError());
-    } else if (s->fp64) {
-        pack_positions<double><<<g, BLOCK, 0, s->stream>>>((float2 *)s->aos_dev, (const double2 *)s->pos[s->cur], (uint32_t)s->i_begin, ic);
-        HIPCHK(hipGetLastError());
-    } else {
-        src = (const float2 *)s->pos[s->cur] + s->i_begin;        // fp32 2-D positions are already (x, y) floats
-    }
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        const vec *pos = (const vec *)s->pos[s->cur];
+        if constexpr (L.dims3)
+            pack_positions3<real><<<g, BLOCK, 0, s->stream>>>((float *)s->aos_dev, pos, (uint32_t)s->i_begin, ic);
+        else if constexpr (std::is_same_v<real, double>)
+            pack_positions<real><<<g, BLOCK, 0, s->stream>>>((float2 *)s->aos_dev, pos, (uint32_t)s->i_begin, ic);
+        else
+            src = pos + s->i_begin;                        // fp32 2-D positions are already (x, y) floats: no kernel
+    });
+    if (src == s->aos_dev) HIPCHK(hipGetLastError());      // a pack kernel ran
     return copy_d2h(s, out_xy, src, bytes, s->stream, s->staging);
 }
 
@@ -1660,20 +1550,17 @@ extern "C" int nb_energy(nb_sim *s, double *kinetic, double *potential)
     if (bind(s)) return NB_EHIP;
     const uint32_t g = (uint32_t)s->ered_blocks;
     const double eps2 = (double)s->p.eps * (double)s->p.eps;
-    if (s->dims3 && s->fp64)
-        energy_partials3<double><<<g, BLOCK, 0, s->stream>>>((const double4 *)s->pos[s->cur], (const double4 *)s->vel, (uint32_t)s->n,
-                                                             (uint32_t)s->i_begin, (uint32_t)s->i_count, eps2, s->ered_dev, s->ered_dev + g);
-    else if (s->dims3)
-        energy_partials3<float><<<g, BLOCK, 0, s->stream>>>((const float4 *)s->pos[s->cur], (const float4 *)s->vel, (uint32_t)s->n,
-                                                            (uint32_t)s->i_begin, (uint32_t)s->i_count, eps2, s->ered_dev, s->ered_dev + g);
-    else if (s->fp64)
-        energy_partials<double><<<g, BLOCK, 0, s->stream>>>((const double2 *)s->pos[s->cur], (const double *)s->mass, (const double2 *)s->vel,
-                                                            (uint32_t)s->n, (uint32_t)s->i_begin, (uint32_t)s->i_count, eps2,
-                                                            s->ered_dev, s->ered_dev + g);
-    else
-        energy_partials<float><<<g, BLOCK, 0, s->stream>>>((const float2 *)s->pos[s->cur], (const float *)s->mass, (const float2 *)s->vel,
-                                                           (uint32_t)s->n, (uint32_t)s->i_begin, (uint32_t)s->i_count, eps2,
-                                                           s->ered_dev, s->ered_dev + g);
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        const vec *pos = (const vec *)s->pos[s->cur], *vel = (const vec *)s->vel;
+        if constexpr (L.dims3)
+            energy_partials3<real><<<g, BLOCK, 0, s->stream>>>(pos, vel, (uint32_t)s->n, (uint32_t)s->i_begin, (uint32_t)s->i_count, eps2,
+                                                               s->ered_dev, s->ered_dev + g);
+        else
+            energy_partials<real><<<g, BLOCK, 0, s->stream>>>(pos, (const real *)s->mass, vel, (uint32_t)s->n, (uint32_t)s->i_begin,
+                                                              (uint32_t)s->i_count, eps2, s->ered_dev, s->ered_dev + g);
+    });
     HIPCHK(hipGetLastError());
     std::vector<double> h(2 * (size_t)g);
     { const int rc = copy_d2h(s, h.data(), s->ered_dev, h.size() * sizeof(double)); if (rc) return rc; }
@@ -1690,16 +1577,15 @@ extern "C" int nb_momentum(nb_sim *s, double *p_xyz, double *l_z)
     if (bind(s)) return NB_EHIP;
     const uint32_t g = (uint32_t)s->ered_blocks;
     if (!s->pred_dev) HIPCHK(hipMalloc((void **)&s->pred_dev, 4 * (size_t)g * sizeof(double)));
-    if (s->dims3 && s->fp64)
-        momentum_partials3<double><<<g, BLOCK, 0, s->stream>>>((const double4 *)s->pos[s->cur], (const double4 *)s->vel, (uint32_t)s->i_begin, (uint32_t)s->i_count, s->pred_dev);
-    else if (s->dims3)
-        momentum_partials3<float><<<g, BLOCK, 0, s->stream>>>((const float4 *)s->pos[s->cur], (const float4 *)s->vel, (uint32_t)s->i_begin, (uint32_t)s->i_count, s->pred_dev);
-    else if (s->fp64)
-        momentum_partials<double><<<g, BLOCK, 0, s->stream>>>((const double2 *)s->pos[s->cur], (const double *)s->mass, (const double2 *)s->vel,
-                                                              (uint32_t)s->i_begin, (uint32_t)s->i_count, s->pred_dev);
-    else
-        momentum_partials<float><<<g, BLOCK, 0, s->stream>>>((const float2 *)s->pos[s->cur], (const float *)s->mass, (const float2 *)s->vel,
-                                                             (uint32_t)s->i_begin, (uint32_t)s->i_count, s->pred_dev);
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        const vec *pos = (const vec *)s->pos[s->cur], *vel = (const vec *)s->vel;
+        if constexpr (L.dims3)
+            momentum_partials3<real><<<g, BLOCK, 0, s->stream>>>(pos, vel, (uint32_t)s->i_begin, (uint32_t)s->i_count, s->pred_dev);
+        else
+            momentum_partials<real><<<g, BLOCK, 0, s->stream>>>(pos, (const real *)s->mass, vel, (uint32_t)s->i_begin, (uint32_t)s->i_count, s->pred_dev);
+    });
     HIPCHK(hipGetLastError());
     std::vector<double> h(4 * (size_t)g);
     { const int rc = copy_d2h(s, h.data(), s->pred_dev, h.size() * sizeof(double)); if (rc) return rc; }
@@ -1795,7 +1681,7 @@ extern "C" int nb_exchange_accelerations(nb_sim *const *sims, int count)
     if (!sims || count < 1 || count > 64) return nb_fail(NB_EINVAL, "nb_exchange_accelerations: 1..64 handles");
     PartialPtrs src;
     for (int a = 0; a < count; ++a) {
-        if (!sims[a] || !sims[a]->sym_sharded || sims[a]->n != sims[0]->n || sims[a]->esz != sims[0]->esz ||
+        if (!sims[a] || sims[a]->path != StepPath::SYM_SHARDED || sims[a]->n != sims[0]->n || sims[a]->esz != sims[0]->esz ||
             sims[a]->p.shard_world != count || sims[a]->p.shard_rank != a) {
             return nb_fail(NB_EINVAL, "nb_exchange_accelerations: needs the `count` handles of one symmetric sharded run, in rank order");
         }
@@ -1808,10 +1694,10 @@ extern "C" int nb_exchange_accelerations(nb_sim *const *sims, int count)
         if (bind(s)) return NB_EHIP;
         if ((rc = enable_peers(s, sims, count))) return rc;
         const uint32_t ic = (uint32_t)s->i_count, g = (ic + BLOCK - 1) / BLOCK;
-        if (s->dims3 && s->fp64) sum_partials<double4><<<g, BLOCK, 0, s->stream>>>(src, count, (uint32_t)s->i_begin, ic, (double4 *)s->acc_owned);
-        else if (s->dims3)       sum_partials<float4><<<g, BLOCK, 0, s->stream>>>(src, count, (uint32_t)s->i_begin, ic, (float4 *)s->acc_owned);
-        else if (s->fp64)        sum_partials<double2><<<g, BLOCK, 0, s->stream>>>(src, count, (uint32_t)s->i_begin, ic, (double2 *)s->acc_owned);
-        else                     sum_partials<float2><<<g, BLOCK, 0, s->stream>>>(src, count, (uint32_t)s->i_begin, ic, (float2 *)s->acc_owned);
+        with_layout(s, [&](auto L) {
+            using vec = typename decltype(L)::vec;
+            sum_partials<vec><<<g, BLOCK, 0, s->stream>>>(src, count, (uint32_t)s->i_begin, ic, (vec *)s->acc_owned);
+        });
         HIPCHK(hipGetLastError());
     }
     return cross_fence(sims, count, 1);                          // acc_full may be rewritten only after every peer has read it
@@ -1820,9 +1706,9 @@ extern "C" int nb_exchange_accelerations(nb_sim *const *sims, int count)
 extern "C" int nb_shard_protocol(const nb_sim *s)
 {
     if (!s) return NB_SHARD_NONE;
-    if (s->sym_replicated) return NB_SHARD_ALLREDUCE;
-    if (s->sym_sharded) return NB_SHARD_SYMMETRIC;          // also the single-rank form (NB_FLAG_SHARD_SINGLE: i_count == n)
-    return s->i_count == s->n ? NB_SHARD_NONE : NB_SHARD_ALLGATHER;
+    if (s->path == StepPath::SYM_REPLICATED) return NB_SHARD_ALLREDUCE;
+    if (s->path == StepPath::SYM_SHARDED) return NB_SHARD_SYMMETRIC;   // also the single-rank form (NB_FLAG_SHARD_SINGLE: i_count == n)
+    return s->i_count == s->n ? NB_SHARD_NONE : NB_SHARD_ALLGATHER;    // TWO_PHASE, and a sharded ONE_SIDED handle (sequential order)
 }
 
 // In-process all-reduce of the replicated protocol (a host that drives all `count` handles of one run itself):
@@ -1833,7 +1719,7 @@ extern "C" int nb_exchange_allreduce(nb_sim *const *sims, int count)
     if (!sims || count < 1 || count > 64) return nb_fail(NB_EINVAL, "nb_exchange_allreduce: 1..64 handles");
     PartialPtrs src;
     for (int a = 0; a < count; ++a) {
-        if (!sims[a] || !sims[a]->sym_replicated || sims[a]->n != sims[0]->n || sims[a]->esz != sims[0]->esz ||
+        if (!sims[a] || sims[a]->path != StepPath::SYM_REPLICATED || sims[a]->n != sims[0]->n || sims[a]->esz != sims[0]->esz ||
             sims[a]->p.shard_world != count || sims[a]->p.shard_rank != a)
             return nb_fail(NB_EINVAL, "nb_exchange_allreduce: needs the `count` handles of one replicated (NB_FLAG_SHARD_ALLREDUCE) run, in rank order");
         src.p[a] = sims[a]->acc_full;
@@ -1845,10 +1731,10 @@ extern "C" int nb_exchange_allreduce(nb_sim *const *sims, int count)
         if (bind(s)) return NB_EHIP;
         if ((rc = enable_peers(s, sims, count))) return rc;
         const uint32_t nn = (uint32_t)s->n, g = (nn + BLOCK - 1) / BLOCK;
-        if (s->dims3 && s->fp64) sum_partials<double4><<<g, BLOCK, 0, s->stream>>>(src, count, 0u, nn, (double4 *)s->partial);
-        else if (s->dims3)       sum_partials<float4><<<g, BLOCK, 0, s->stream>>>(src, count, 0u, nn, (float4 *)s->partial);
-        else if (s->fp64)        sum_partials<double2><<<g, BLOCK, 0, s->stream>>>(src, count, 0u, nn, (double2 *)s->partial);
-        else                     sum_partials<float2><<<g, BLOCK, 0, s->stream>>>(src, count, 0u, nn, (float2 *)s->partial);
+        with_layout(s, [&](auto L) {
+            using vec = typename decltype(L)::vec;
+            sum_partials<vec><<<g, BLOCK, 0, s->stream>>>(src, count, 0u, nn, (vec *)s->partial);
+        });
         HIPCHK(hipGetLastError());
     }
     if ((rc = cross_fence(sims, count, 1))) return rc;           // ... and only when every handle has read every input
@@ -1861,14 +1747,14 @@ extern "C" int nb_exchange_allreduce(nb_sim *const *sims, int count)
 }
 extern "C" void *nb_acc_buffer(nb_sim *s, int which)
 {
-    if (!s || !(s->sym_sharded || s->sym_replicated)) return nullptr;
+    if (!s || (s->path != StepPath::SYM_SHARDED && s->path != StepPath::SYM_REPLICATED)) return nullptr;
     return which == 0 ? s->acc_full : s->acc_owned;
 }
 
 extern "C" int nb_dump(nb_sim *s, const char *path)
 {
     if (!s || !path) return nb_fail(NB_EINVAL, "nb_dump: NULL argument");
-    if (sharded(s)) return nb_fail(NB_ESTATE, "nb_dump: sharded handle holds only its block; gather on the host and use nb_write_bodies");
+    if (s->i_count != s->n) return nb_fail(NB_ESTATE, "nb_dump: sharded handle holds only its block; gather on the host and use nb_write_bodies");
     std::vector<nb_body> host(s->n);
     int rc = nb_sync(s, host.data());
     if (rc) return rc;
@@ -1950,7 +1836,7 @@ extern "C" int nb_sym_plan_info(const nb_sim *s, nb_sym_info *out)
 {
     if (!s || !out) return nb_fail(NB_EINVAL, "nb_sym_plan_info: NULL argument");
     if (out->struct_size != sizeof(nb_sym_info)) return nb_fail(NB_EINVAL, "nb_sym_plan_info: out->struct_size %u != %zu", out->struct_size, sizeof(nb_sym_info));
-    if (s->sym || s->sym_sharded || s->sym_replicated) *out = s->sym_info;
+    if (symmetric(s)) *out = s->sym_info;
     else { memset(out, 0, sizeof *out); out->struct_size = (uint32_t)sizeof(nb_sym_info); out->cus = (uint32_t)s->cus; }
     return NB_OK;
 }
@@ -1968,8 +1854,7 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
              BLOCK, (seq || s->fp64) ? 1 : F32_WS, seq ? 1 : (s->fp64 ? a.P : 2 * a.P), a.i_tiles, a.js,
              seq ? a.i_tiles : grid_blocks(a.i_tiles, a.js), TJ,
              s->job_local.P, s->job_local.js, s->job_remote.P, s->job_remote.js, (int)s->uniform_mass, (int)s->mass_scaled, (double)s->mass_scaling_dev,
-             (int)(s->sym || s->sym_sharded || s->sym_replicated), s->sym_sb,
-             (int)(s->sym_pairs && !s->mass_scaled && (!s->dims3 || s->uniform_mass || s->p.sym_chunk_pairs > 0)), s->sym_items, s->sym_L, s->sym_items_late,
+             (int)symmetric(s), s->sym_sb, (int)sym_uses_pairs(s), s->sym_items, s->sym_L, s->sym_items_late,
              (double)s->sym_info.slab_s_bytes / 1048576.0, (double)s->sym_info.slab_r_bytes / 1048576.0, s->cus);
     return NB_OK;
 }
