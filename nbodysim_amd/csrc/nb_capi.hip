@@ -166,15 +166,6 @@ static int bind(const nb_sim *s)
 // ---------------------------------------------------------------------------
 // dispatch: run-time choices -> template arguments
 // ---------------------------------------------------------------------------
-// Element layout of a handle: real type, the vector of one position / velocity / acceleration / slab element
-// (real2 in 2-D, real4 {x,y,z,m} in 3-D), and whether it is 3-D.  2-D handles also keep a separate `mass` array.
-template <typename R, bool D3>
-struct Layout {
-    using real = R;
-    using vec = std::conditional_t<D3, typename vec4_of<R>::type, typename vec2_of<R>::type>;
-    static constexpr bool dims3 = D3;
-};
-
 // f(Layout<...>{}) for the handle's precision and dimensionality: the one place that maps them to types.
 template <typename F>
 static auto with_layout(const nb_sim *s, F &&f)
@@ -773,13 +764,9 @@ static int do_upload(nb_sim *s, const nb_body *in)
     with_layout(s, [&](auto L) {
         using real = typename decltype(L)::real;
         using vec = typename decltype(L)::vec;
-        for (int b = 0; b < 2; ++b) {      // both replicas get the full initial positions
-            if constexpr (L.dims3)
-                unpack_bodies3<real><<<g, BLOCK, 0, s->stream>>>(s->aos_dev, n, (vec *)s->pos[b], (vec *)s->vel, (vec *)s->acc, s->radius, ib, ic);
-            else
-                unpack_bodies<real><<<g, BLOCK, 0, s->stream>>>(s->aos_dev, n, (vec *)s->pos[b], (real *)s->mass, (vec *)s->vel, (vec *)s->acc,
-                                                                s->radius, ib, ic);
-        }
+        for (int b = 0; b < 2; ++b)        // both replicas get the full initial positions
+            unpack_bodies<decltype(L)><<<g, BLOCK, 0, s->stream>>>(s->aos_dev, n, (vec *)s->pos[b], (real *)s->mass, (vec *)s->vel, (vec *)s->acc,
+                                                                   s->radius, ib, ic);
     });
     HIPCHK(hipGetLastError());
     if (forced_scaling || auto_scaling) {
@@ -1162,16 +1149,12 @@ static int launch_integrate(nb_sim *s, const void *src, uint32_t nslabs, uint32_
         using vec = typename decltype(L)::vec;
         const vec *pc = (const vec *)s->pos[s->cur], *sl = (const vec *)src;
         vec *pn = (vec *)s->pos[s->cur ^ 1], *vel = (vec *)s->vel, *acc = (vec *)s->acc;
-        if constexpr (L.dims3) {
-            integrate3<real><<<g, BLOCK, 0, s->stream>>>(pc, pn, vel, acc, sl, nslabs, first, cnt, (real)dt_kick, (real)dt_drift, flags);
-        } else {
-            auto go = [&](auto kernel) {
-                kernel<<<g, BLOCK, 0, s->stream>>>(pc, pn, vel, acc, sl, nslabs, first, cnt, (real)dt_kick, (real)dt_drift, s->p.extras, flags);
-            };
-            if constexpr (std::is_same_v<real, float>)
-                if (strict) return go(integrate<float, true>);      // the sequential order's strict form: fp32 2-D only
-            go(integrate<real, false>);
-        }
+        auto go = [&](auto kernel) {
+            kernel<<<g, BLOCK, 0, s->stream>>>(pc, pn, vel, acc, sl, nslabs, first, cnt, (real)dt_kick, (real)dt_drift, s->p.extras, flags);
+        };
+        if constexpr (std::is_same_v<real, float> && !L.dims3)
+            if (strict) return go(integrate<decltype(L), true>);   // the sequential order's strict form: fp32 2-D only
+        go(integrate<decltype(L), false>);
     });
     HIPCHK(hipGetLastError());
     return NB_OK;
@@ -1438,10 +1421,8 @@ static int launch_pack_range(nb_sim *s, BodyRec *out, uint32_t o, uint32_t cnt)
         using real = typename decltype(L)::real;
         using vec = typename decltype(L)::vec;
         const vec *pos = (const vec *)s->pos[s->cur];
-        if constexpr (L.dims3)
-            pack_bodies3<real><<<g, BLOCK, 0, s->stream>>>(out, pos, (const vec *)vel, (const vec *)acc, s->radius, ib, cnt);
-        else
-            pack_bodies<real><<<g, BLOCK, 0, s->stream>>>(out, pos, (const real *)s->mass, (const vec *)vel, (const vec *)acc, s->radius, ib, cnt);
+        pack_bodies<decltype(L)><<<g, BLOCK, 0, s->stream>>>(out, pos, (const real *)s->mass, (const vec *)vel, (const vec *)acc, s->radius,
+                                                             ib, cnt);
     });
     HIPCHK(hipGetLastError());
     return NB_OK;
@@ -1533,10 +1514,8 @@ extern "C" int nb_sync_positions(nb_sim *s, float *out_xy)
         using real = typename decltype(L)::real;
         using vec = typename decltype(L)::vec;
         const vec *pos = (const vec *)s->pos[s->cur];
-        if constexpr (L.dims3)
-            pack_positions3<real><<<g, BLOCK, 0, s->stream>>>((float *)s->aos_dev, pos, (uint32_t)s->i_begin, ic);
-        else if constexpr (std::is_same_v<real, double>)
-            pack_positions<real><<<g, BLOCK, 0, s->stream>>>((float2 *)s->aos_dev, pos, (uint32_t)s->i_begin, ic);
+        if constexpr (L.dims3 || std::is_same_v<real, double>)
+            pack_positions<decltype(L)><<<g, BLOCK, 0, s->stream>>>((float *)s->aos_dev, pos, (uint32_t)s->i_begin, ic);
         else
             src = pos + s->i_begin;                        // fp32 2-D positions are already (x, y) floats: no kernel
     });
@@ -1554,12 +1533,8 @@ extern "C" int nb_energy(nb_sim *s, double *kinetic, double *potential)
         using real = typename decltype(L)::real;
         using vec = typename decltype(L)::vec;
         const vec *pos = (const vec *)s->pos[s->cur], *vel = (const vec *)s->vel;
-        if constexpr (L.dims3)
-            energy_partials3<real><<<g, BLOCK, 0, s->stream>>>(pos, vel, (uint32_t)s->n, (uint32_t)s->i_begin, (uint32_t)s->i_count, eps2,
-                                                               s->ered_dev, s->ered_dev + g);
-        else
-            energy_partials<real><<<g, BLOCK, 0, s->stream>>>(pos, (const real *)s->mass, vel, (uint32_t)s->n, (uint32_t)s->i_begin,
-                                                              (uint32_t)s->i_count, eps2, s->ered_dev, s->ered_dev + g);
+        energy_partials<decltype(L)><<<g, BLOCK, 0, s->stream>>>(pos, (const real *)s->mass, vel, (uint32_t)s->n, (uint32_t)s->i_begin,
+                                                                 (uint32_t)s->i_count, eps2, s->ered_dev, s->ered_dev + g);
     });
     HIPCHK(hipGetLastError());
     std::vector<double> h(2 * (size_t)g);
@@ -1581,10 +1556,8 @@ extern "C" int nb_momentum(nb_sim *s, double *p_xyz, double *l_z)
         using real = typename decltype(L)::real;
         using vec = typename decltype(L)::vec;
         const vec *pos = (const vec *)s->pos[s->cur], *vel = (const vec *)s->vel;
-        if constexpr (L.dims3)
-            momentum_partials3<real><<<g, BLOCK, 0, s->stream>>>(pos, vel, (uint32_t)s->i_begin, (uint32_t)s->i_count, s->pred_dev);
-        else
-            momentum_partials<real><<<g, BLOCK, 0, s->stream>>>(pos, (const real *)s->mass, vel, (uint32_t)s->i_begin, (uint32_t)s->i_count, s->pred_dev);
+        momentum_partials<decltype(L)><<<g, BLOCK, 0, s->stream>>>(pos, (const real *)s->mass, vel, (uint32_t)s->i_begin, (uint32_t)s->i_count,
+                                                                   s->pred_dev);
     });
     HIPCHK(hipGetLastError());
     std::vector<double> h(4 * (size_t)g);

@@ -18,9 +18,12 @@
 //   sym_gather / integrate          fixed-order sums of the partial slabs + kick/drift (no atomics:
 //                                   results are reproducible run to run)
 //   pack/unpack/energy/sum_partials AoS <-> SoA, diagnostics, in-process reduce-scatter
+// integrate, kick/drift, pack/unpack, energy and momentum are keyed on a Layout (precision x 2-D / 3-D) and
+// serve the 3-D handles too; the 3-D force kernels and their gather are in nb_kernels3d.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "nb_plan.h"   // SymItem, SymCov, SYM_SB, SYM_CH: shared with the host-side planner
 
@@ -42,6 +45,31 @@ constexpr float PAD_XY = 1.0e18f;
 template <typename real> struct vec2_of;
 template <> struct vec2_of<float> { typedef float2 type; };
 template <> struct vec2_of<double> { typedef double2 type; };
+
+template <typename real> struct vec4_of;
+template <> struct vec4_of<float> { typedef float4 type; };
+template <> struct vec4_of<double> { typedef double4 type; };
+
+template <typename real> __device__ __forceinline__ typename vec4_of<real>::type make_real4(real x, real y, real z, real w);
+template <> __device__ __forceinline__ float4 make_real4<float>(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
+template <> __device__ __forceinline__ double4 make_real4<double>(double x, double y, double z, double w) { return make_double4(x, y, z, w); }
+
+// Element layout of a handle: real type, the vector of one position / velocity / acceleration / slab element
+// (real2 in 2-D, real4 {x,y,z,m} in 3-D), and whether it is 3-D.  2-D handles also keep a separate `mass` array.
+template <typename R, bool D3>
+struct Layout {
+    using real = R;
+    using vec = std::conditional_t<D3, typename vec4_of<R>::type, typename vec2_of<R>::type>;
+    static constexpr bool dims3 = D3;
+};
+
+// the mass of particle i: the separate array in 2-D, pos.w in 3-D
+template <typename L>
+__device__ __forceinline__ typename L::real mass_at(const typename L::vec *__restrict__ pos, const typename L::real *__restrict__ mass, uint32_t i)
+{
+    if constexpr (L::dims3) return pos[i].w;
+    else return mass[i];
+}
 
 // Slab stores of the symmetric kernels.  WT = write-through (`sc1`): the bytes leave this XCD's L2 for memory at once instead of
 // staying dirty there until the kernel's end flushes them — the partials are read by the NEXT launch only (force_sym_f32 below:
@@ -115,22 +143,28 @@ __device__ __forceinline__ double exp_like_reference(double x) { return exp(x); 
 // [soft boundary :140-155]; x_next = x + v dt.  STRICT keeps every operation individually
 // rounded (the reference build has no FMA contraction) for bit parity.
 // flags: INTEG_KICK applies the kick (+extras), INTEG_DRIFT writes pos_next; 0 = store acc only.
+// In 3-D the mass travels in x.w and the extras (defined by the reference in the plane only) are not applied;
+// nb_create refuses 3-D with extras or the sequential order, so STRICT is 2-D only.
 // ---------------------------------------------------------------------------
 enum { INTEG_KICK = 1, INTEG_DRIFT = 2 };
 
 // v, x: the particle's velocity and position, loaded by the caller (sym_gather_block loads them before it sums, so that the
 // two loads are not one more memory latency at the end of a latency-bound kernel); unused unless flags has INTEG_KICK.
-template <typename real, bool STRICT>
+// ACC = false: the caller has stored acc and checked INTEG_KICK itself.
+template <typename L, bool STRICT, bool ACC = true>
 __device__ __forceinline__
-void kick_drift_loaded(typename vec2_of<real>::type a, typename vec2_of<real>::type v, const typename vec2_of<real>::type x, uint32_t li,
-                       typename vec2_of<real>::type *__restrict__ pos_next,
-                       typename vec2_of<real>::type *__restrict__ vel,
-                       typename vec2_of<real>::type *__restrict__ acc,
-                       uint32_t i_begin, real dt_kick, real dt_drift, int extras, int flags)
+void kick_drift_loaded(typename L::vec a, typename L::vec v, const typename L::vec x, uint32_t li,
+                       typename L::vec *__restrict__ pos_next,
+                       typename L::vec *__restrict__ vel,
+                       typename L::vec *__restrict__ acc,
+                       uint32_t i_begin, typename L::real dt_kick, typename L::real dt_drift, int extras, int flags)
 {
-    typedef typename vec2_of<real>::type real2;
-    acc[li] = a;
-    if (!(flags & INTEG_KICK)) return;              // acceleration gather only
+    static_assert(!(L::dims3 && STRICT), "the strict form is the 2-D sequential order's");
+    typedef typename L::real real;
+    if constexpr (ACC) {
+        acc[li] = a;
+        if (!(flags & INTEG_KICK)) return;          // acceleration gather only
+    }
     if constexpr (STRICT) {
 #pragma clang fp contract(off)
         v.x += a.x * dt_kick;                       // Simulation.hpp:130-131
@@ -138,35 +172,38 @@ void kick_drift_loaded(typename vec2_of<real>::type a, typename vec2_of<real>::t
     } else {
         v.x = __builtin_fma(a.x, dt_kick, v.x);
         v.y = __builtin_fma(a.y, dt_kick, v.y);
+        if constexpr (L::dims3) v.z = __builtin_fma(a.z, dt_kick, v.z);
     }
-    if (extras & 1) {                               // Simulation.hpp:133-137
+    if constexpr (!L::dims3) {
+        if (extras & 1) {                           // Simulation.hpp:133-137
 #pragma clang fp contract(off)
-        const real MAX_VELOCITY = (real)1000.0;
-        const real vm = v.x * v.x + v.y * v.y;
-        if (vm > MAX_VELOCITY * MAX_VELOCITY) {
-            const real scale = MAX_VELOCITY / sqrt(vm);
-            v.x *= scale; v.y *= scale;
+            const real MAX_VELOCITY = (real)1000.0;
+            const real vm = v.x * v.x + v.y * v.y;
+            if (vm > MAX_VELOCITY * MAX_VELOCITY) {
+                const real scale = MAX_VELOCITY / sqrt(vm);
+                v.x *= scale; v.y *= scale;
+            }
         }
-    }
-    if (extras & 2) {                               // Simulation.hpp:140-155
+        if (extras & 2) {                           // Simulation.hpp:140-155
 #pragma clang fp contract(off)
-        const real SOFT_BOUNDARY = (real)80000.0;   // 100000.0f * 0.8f
-        const real d2 = x.x * x.x + x.y * x.y;
-        if (d2 > SOFT_BOUNDARY * SOFT_BOUNDARY) {
-            const real dist = sqrt(d2);
-            const real ratio = dist / SOFT_BOUNDARY;
-            const real force = (real)0.9f * exp_like_reference(ratio - (real)1.0);   // std::exp(float) = glibc's expf, restated above
-            const real k = (real)-1.0 / dist;
-            const real fdt = force * dt_kick;
-            v.x += (x.x * k) * fdt;
-            v.y += (x.y * k) * fdt;
-            v.x *= (real)0.9995f;
-            v.y *= (real)0.9995f;
+            const real SOFT_BOUNDARY = (real)80000.0;   // 100000.0f * 0.8f
+            const real d2 = x.x * x.x + x.y * x.y;
+            if (d2 > SOFT_BOUNDARY * SOFT_BOUNDARY) {
+                const real dist = sqrt(d2);
+                const real ratio = dist / SOFT_BOUNDARY;
+                const real force = (real)0.9f * exp_like_reference(ratio - (real)1.0);   // std::exp(float) = glibc's expf, restated above
+                const real k = (real)-1.0 / dist;
+                const real fdt = force * dt_kick;
+                v.x += (x.x * k) * fdt;
+                v.y += (x.y * k) * fdt;
+                v.x *= (real)0.9995f;
+                v.y *= (real)0.9995f;
+            }
         }
     }
     vel[li] = v;
     if (flags & INTEG_DRIFT) {
-        real2 xn;
+        typename L::vec xn;
         if constexpr (STRICT) {
 #pragma clang fp contract(off)
             xn.x = x.x + v.x * dt_drift;            // Simulation.hpp:161-162
@@ -174,24 +211,36 @@ void kick_drift_loaded(typename vec2_of<real>::type a, typename vec2_of<real>::t
         } else {
             xn.x = __builtin_fma(v.x, dt_drift, x.x);
             xn.y = __builtin_fma(v.y, dt_drift, x.y);
+            if constexpr (L::dims3) {
+                xn.z = __builtin_fma(v.z, dt_drift, x.z);
+                xn.w = x.w;                         // the mass travels with the position
+            }
         }
         pos_next[i_begin + li] = xn;
     }
 }
 
-template <typename real, bool STRICT>
+template <typename L, bool STRICT>
 __device__ __forceinline__
-void kick_drift_one(typename vec2_of<real>::type a, uint32_t li,
-                    const typename vec2_of<real>::type *__restrict__ pos_cur,
-                    typename vec2_of<real>::type *__restrict__ pos_next,
-                    typename vec2_of<real>::type *__restrict__ vel,
-                    typename vec2_of<real>::type *__restrict__ acc,
-                    uint32_t i_begin, real dt_kick, real dt_drift, int extras, int flags)
+void kick_drift_one(typename L::vec a, uint32_t li,
+                    const typename L::vec *__restrict__ pos_cur,
+                    typename L::vec *__restrict__ pos_next,
+                    typename L::vec *__restrict__ vel,
+                    typename L::vec *__restrict__ acc,
+                    uint32_t i_begin, typename L::real dt_kick, typename L::real dt_drift, int extras, int flags)
 {
-    typename vec2_of<real>::type v, x;
-    v.x = v.y = x.x = x.y = 0;
-    if (flags & INTEG_KICK) { v = vel[li]; x = pos_cur[i_begin + li]; }
-    kick_drift_loaded<real, STRICT>(a, v, x, li, pos_next, vel, acc, i_begin, dt_kick, dt_drift, extras, flags);
+    if constexpr (L::dims3) {
+        // acc is stored before v and x are loaded: loaded first, the real4 pair would hold 8 (fp32) / 12 (fp64) more VGPRs
+        a.w = 0;
+        acc[li] = a;
+        if (!(flags & INTEG_KICK)) return;
+        kick_drift_loaded<L, STRICT, false>(a, vel[li], pos_cur[i_begin + li], li, pos_next, vel, acc, i_begin, dt_kick, dt_drift, extras, flags);
+    } else {
+        typename L::vec v, x;
+        v.x = v.y = x.x = x.y = 0;
+        if (flags & INTEG_KICK) { v = vel[li]; x = pos_cur[i_begin + li]; }
+        kick_drift_loaded<L, STRICT>(a, v, x, li, pos_next, vel, acc, i_begin, dt_kick, dt_drift, extras, flags);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1005,7 +1054,7 @@ void sym_gather_block(uint32_t blk,
 #pragma unroll
         for (int j = 1; j < GATHER_Q; ++j) { t.x += part[j][f].x; t.y += part[j][f].y; }
         if (base) { const real2 bb = base[lf]; t.x += bb.x; t.y += bb.y; }
-        if constexpr (FUSE) kick_drift_loaded<real, false>(t, vf, xf, lf, pos_next, vel, acc, k0, dt_kick, dt_drift, extras, flags);
+        if constexpr (FUSE) kick_drift_loaded<Layout<real, false>, false>(t, vf, xf, lf, pos_next, vel, acc, k0, dt_kick, dt_drift, extras, flags);
         else acc_sum[k0 + lf] = t;
     }
 }
@@ -1318,6 +1367,12 @@ void force_tiled_f64(const double2 *__restrict__ pos, const double *__restrict__
         if (li[p] < i_count) out[li[p]] = make_double2(ax[p], ay[p]);
 }
 
+// a += b over the components (x, y [, z]); w, the 3-D mass slot, is left as it is
+__device__ __forceinline__ void add_to(float2 &a, const float2 &b) { a.x += b.x; a.y += b.y; }
+__device__ __forceinline__ void add_to(double2 &a, const double2 &b) { a.x += b.x; a.y += b.y; }
+__device__ __forceinline__ void add_to(float4 &a, const float4 &b) { a.x += b.x; a.y += b.y; a.z += b.z; }
+__device__ __forceinline__ void add_to(double4 &a, const double4 &b) { a.x += b.x; a.y += b.y; a.z += b.z; }
+
 // ---------------------------------------------------------------------------
 // integrate — Simulation::iterate after attract(), Simulation.hpp:129-163, for
 // the owned block: a = sum of slabs (fixed order); v += a dt; [clamp];
@@ -1327,26 +1382,21 @@ void force_tiled_f64(const double2 *__restrict__ pos, const double *__restrict__
 // flags: INTEG_KICK applies the kick (+extras), INTEG_DRIFT writes pos_next;
 // flags = 0 only gathers the slabs into acc (nb_accelerations, KDK bootstrap).
 // ---------------------------------------------------------------------------
-
-template <typename real, bool STRICT>
+template <typename L, bool STRICT>
 __global__ __launch_bounds__(BLOCK)
-void integrate(const typename vec2_of<real>::type *__restrict__ pos_cur,
-               typename vec2_of<real>::type *__restrict__ pos_next,
-               typename vec2_of<real>::type *__restrict__ vel,
-               typename vec2_of<real>::type *__restrict__ acc,
-               const typename vec2_of<real>::type *__restrict__ partial,
+void integrate(const typename L::vec *__restrict__ pos_cur,
+               typename L::vec *__restrict__ pos_next,
+               typename L::vec *__restrict__ vel,
+               typename L::vec *__restrict__ acc,
+               const typename L::vec *__restrict__ partial,
                uint32_t nslabs, uint32_t i_begin, uint32_t i_count,
-               real dt_kick, real dt_drift, int extras, int flags)
+               typename L::real dt_kick, typename L::real dt_drift, int extras, int flags)
 {
-    typedef typename vec2_of<real>::type real2;
     const uint32_t li = blockIdx.x * BLOCK + threadIdx.x;
     if (li >= i_count) return;
-    real2 a = partial[li];
-    for (uint32_t s = 1; s < nslabs; ++s) {
-        const real2 b = partial[(size_t)s * i_count + li];
-        a.x += b.x; a.y += b.y;
-    }
-    kick_drift_one<real, STRICT>(a, li, pos_cur, pos_next, vel, acc, i_begin, dt_kick, dt_drift, extras, flags);
+    typename L::vec a = partial[li];
+    for (uint32_t s = 1; s < nslabs; ++s) add_to(a, partial[(size_t)s * i_count + li]);
+    kick_drift_one<L, STRICT>(a, li, pos_cur, pos_next, vel, acc, i_begin, dt_kick, dt_drift, extras, flags);
 }
 
 // ---------------------------------------------------------------------------
@@ -1355,11 +1405,6 @@ void integrate(const typename vec2_of<real>::type *__restrict__ pos_cur,
 // handles' acc_full pointers (peer-accessible device memory); T is the element type.
 // ---------------------------------------------------------------------------
 struct PartialPtrs { const void *p[64]; };
-
-__device__ __forceinline__ void add_to(float2 &a, const float2 &b) { a.x += b.x; a.y += b.y; }
-__device__ __forceinline__ void add_to(double2 &a, const double2 &b) { a.x += b.x; a.y += b.y; }
-__device__ __forceinline__ void add_to(float4 &a, const float4 &b) { a.x += b.x; a.y += b.y; a.z += b.z; }
-__device__ __forceinline__ void add_to(double4 &a, const double4 &b) { a.x += b.x; a.y += b.y; a.z += b.z; }
 
 template <typename T>
 __global__ __launch_bounds__(BLOCK)
@@ -1373,42 +1418,46 @@ void sum_partials(PartialPtrs src, int count, uint32_t first, uint32_t cnt, T *_
 }
 
 // ---------------------------------------------------------------------------
-// AoS (64-byte Body records, Body.hpp:6-13) <-> SoA
+// AoS (64-byte Body records, Body.hpp:6-13) <-> SoA.  3-D: z in the first padding slot of pos / vel / acc,
+// the mass in pos.w (the 2-D `mass` array is not touched)
 // ---------------------------------------------------------------------------
 struct BodyRec { float4 q[4]; };  // pos|pad, vel|pad, acc|pad, mass radius pad pad
 
-template <typename real>
+template <typename L>
 __global__ __launch_bounds__(BLOCK)
 void unpack_bodies(const BodyRec *__restrict__ aos, uint32_t n,
-                   typename vec2_of<real>::type *__restrict__ pos, real *__restrict__ mass,
-                   typename vec2_of<real>::type *__restrict__ vel,
-                   typename vec2_of<real>::type *__restrict__ acc,
+                   typename L::vec *__restrict__ pos, typename L::real *__restrict__ mass,
+                   typename L::vec *__restrict__ vel,
+                   typename L::vec *__restrict__ acc,
                    float *__restrict__ radius,
                    uint32_t i_begin, uint32_t i_count)
 {
-    typedef typename vec2_of<real>::type real2;
+    typedef typename L::real real;
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const float4 p = aos[i].q[0], m = aos[i].q[3];
-    real2 pp; pp.x = (real)p.x; pp.y = (real)p.y;
+    typename L::vec pp; pp.x = (real)p.x; pp.y = (real)p.y;
+    if constexpr (L::dims3) { pp.z = (real)p.z; pp.w = (real)m.x; }
     pos[i] = pp;
-    mass[i] = (real)m.x;
+    if constexpr (!L::dims3) mass[i] = (real)m.x;
     radius[i] = m.y;
     if (i >= i_begin && i - i_begin < i_count) {
         const float4 v = aos[i].q[1], a = aos[i].q[2];
-        real2 vv; vv.x = (real)v.x; vv.y = (real)v.y;
-        real2 aa; aa.x = (real)a.x; aa.y = (real)a.y;
+        typename L::vec vv; vv.x = (real)v.x; vv.y = (real)v.y;
+        if constexpr (L::dims3) { vv.z = (real)v.z; vv.w = 0; }
         vel[i - i_begin] = vv;
+        typename L::vec aa; aa.x = (real)a.x; aa.y = (real)a.y;
+        if constexpr (L::dims3) { aa.z = (real)a.z; aa.w = 0; }
         acc[i - i_begin] = aa;
     }
 }
 
-template <typename real>
+template <typename L>
 __global__ __launch_bounds__(BLOCK)
 void pack_bodies(BodyRec *__restrict__ aos,
-                 const typename vec2_of<real>::type *__restrict__ pos, const real *__restrict__ mass,
-                 const typename vec2_of<real>::type *__restrict__ vel,
-                 const typename vec2_of<real>::type *__restrict__ acc,
+                 const typename L::vec *__restrict__ pos, const typename L::real *__restrict__ mass,
+                 const typename L::vec *__restrict__ vel,
+                 const typename L::vec *__restrict__ acc,
                  const float *__restrict__ radius,
                  uint32_t i_begin, uint32_t i_count)
 {
@@ -1421,19 +1470,25 @@ void pack_bodies(BodyRec *__restrict__ aos,
     r.q[0] = make_float4((float)p.x, (float)p.y, 0.f, 0.f);
     r.q[1] = make_float4((float)v.x, (float)v.y, 0.f, 0.f);
     r.q[2] = make_float4((float)a.x, (float)a.y, 0.f, 0.f);
-    r.q[3] = make_float4((float)mass[i_begin + li], radius[i_begin + li], 0.f, 0.f);
+    if constexpr (L::dims3) { r.q[0].z = (float)p.z; r.q[1].z = (float)v.z; r.q[2].z = (float)a.z; }
+    r.q[3] = make_float4((float)mass_at<L>(pos, mass, i_begin + li), radius[i_begin + li], 0.f, 0.f);
     aos[li] = r;
 }
 
-template <typename real>
+// positions only, as packed floats: (x, y) in 2-D, (x, y, z) in 3-D (the viewer's fast path: 8 / 12 bytes per body)
+template <typename L>
 __global__ __launch_bounds__(BLOCK)
-void pack_positions(float2 *__restrict__ out, const typename vec2_of<real>::type *__restrict__ pos,
+void pack_positions(float *__restrict__ out, const typename L::vec *__restrict__ pos,
                     uint32_t i_begin, uint32_t i_count)
 {
     const uint32_t li = blockIdx.x * BLOCK + threadIdx.x;
     if (li >= i_count) return;
     const auto p = pos[i_begin + li];
-    out[li] = make_float2((float)p.x, (float)p.y);
+    if constexpr (L::dims3) {
+        out[3 * (size_t)li + 0] = (float)p.x;
+        out[3 * (size_t)li + 1] = (float)p.y;
+        out[3 * (size_t)li + 2] = (float)p.z;
+    } else reinterpret_cast<float2 *>(out)[li] = make_float2((float)p.x, (float)p.y);
 }
 
 // ---------------------------------------------------------------------------
@@ -1444,14 +1499,16 @@ void pack_positions(float2 *__restrict__ out, const typename vec2_of<real>::type
 //             handles of a sharded run still add up to the total)
 // Per-block partials are summed on the host in block order (deterministic).
 // ---------------------------------------------------------------------------
-template <typename real>
+template <typename L>
 __global__ __launch_bounds__(BLOCK)
-void energy_partials(const typename vec2_of<real>::type *__restrict__ pos, const real *__restrict__ mass,
-                     const typename vec2_of<real>::type *__restrict__ vel,
+void energy_partials(const typename L::vec *__restrict__ pos, const typename L::real *__restrict__ mass,
+                     const typename L::vec *__restrict__ vel,
                      uint32_t n, uint32_t i_begin, uint32_t i_count, double eps2,
                      double *__restrict__ ksum, double *__restrict__ usum)
 {
-    struct alignas(16) JD { double x, y, m, pad; };
+    struct alignas(16) JD2 { double x, y, m, pad; };
+    struct alignas(16) JD3 { double x, y, z, m; };
+    using JD = std::conditional_t<L::dims3, JD3, JD2>;
     __shared__ JD tile[TJ];
     __shared__ double red[2][BLOCK / 64];
     const uint32_t t = threadIdx.x;
@@ -1459,28 +1516,35 @@ void energy_partials(const typename vec2_of<real>::type *__restrict__ pos, const
     const bool live = li < i_count;
     const uint32_t gi = i_begin + (live ? li : i_count - 1);
     const double xi = (double)pos[gi].x, yi = (double)pos[gi].y;
+    double zi = 0.0;
+    if constexpr (L::dims3) zi = (double)pos[gi].z;
     const double k0375 = vgpr_const(0.375);
     double u = 0.0;
     const uint32_t first = ((i_begin + blockIdx.x * BLOCK) / TJ) * TJ;      // j-tile holding the block's first particle
     for (uint32_t j0 = first; j0 < n; j0 += TJ) {
         const uint32_t j = j0 + t;
         __syncthreads();
-        if (j < n) tile[t] = JD{(double)pos[j].x, (double)pos[j].y, (double)mass[j], 0.0};
-        else tile[t] = JD{0.0, 0.0, 0.0, 0.0};
+        if (j < n) {
+            if constexpr (L::dims3) tile[t] = JD{(double)pos[j].x, (double)pos[j].y, (double)pos[j].z, (double)pos[j].w};
+            else tile[t] = JD{(double)pos[j].x, (double)pos[j].y, (double)mass[j], 0.0};
+        } else tile[t] = JD{0.0, 0.0, 0.0, 0.0};
         __syncthreads();
         const uint32_t cnt = min((uint32_t)TJ, n - j0);
         for (uint32_t jj = 0; jj < cnt; ++jj) {
             const double dx = tile[jj].x - xi, dy = tile[jj].y - yi;
-            const double r2 = __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2));
+            double r2 = __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2));
+            if constexpr (L::dims3) { const double dz = tile[jj].z - zi; r2 = __builtin_fma(dz, dz, r2); }
             const double w = (j0 + jj > gi) ? tile[jj].m : 0.0;
             u = __builtin_fma(w, rsqrt_f64(r2, k0375), u);      // v_rsq_f64 + third-order step: 1.4e-16 relative
         }
     }
     double k = 0.0, uu = 0.0;
     if (live) {
-        const double m = (double)mass[gi];
+        const double m = (double)mass_at<L>(pos, mass, gi);
         const double vx = (double)vel[li].x, vy = (double)vel[li].y;
-        k = 0.5 * m * (vx * vx + vy * vy);
+        double v2 = vx * vx + vy * vy;
+        if constexpr (L::dims3) { const double vz = (double)vel[li].z; v2 += vz * vz; }
+        k = 0.5 * m * v2;
         uu = -m * u;
     }
     // wave64 reduction with shuffles, then across the 4 waves through LDS
@@ -1522,19 +1586,20 @@ __device__ __forceinline__ void block_reduce4(double (&v)[4], double *__restrict
     }
 }
 
-template <typename real>
+template <typename L>
 __global__ __launch_bounds__(BLOCK)
-void momentum_partials(const typename vec2_of<real>::type *__restrict__ pos, const real *__restrict__ mass,
-                       const typename vec2_of<real>::type *__restrict__ vel, uint32_t i_begin, uint32_t i_count,
+void momentum_partials(const typename L::vec *__restrict__ pos, const typename L::real *__restrict__ mass,
+                       const typename L::vec *__restrict__ vel, uint32_t i_begin, uint32_t i_count,
                        double *__restrict__ psum)
 {
     const uint32_t li = blockIdx.x * BLOCK + threadIdx.x;
     double v[4] = {0.0, 0.0, 0.0, 0.0};
     if (li < i_count) {
-        const double m = (double)mass[i_begin + li];
+        const double m = (double)mass_at<L>(pos, mass, i_begin + li);
         const double x = (double)pos[i_begin + li].x, y = (double)pos[i_begin + li].y;
         const double vx = (double)vel[li].x, vy = (double)vel[li].y;
         v[0] = m * vx; v[1] = m * vy; v[3] = m * (x * vy - y * vx);
+        if constexpr (L::dims3) v[2] = m * (double)vel[li].z;
     }
     block_reduce4(v, psum, gridDim.x);
 }

@@ -9,70 +9,17 @@
 //
 // Device layout: positions as real4 {x, y, z, m} (float4: one 16-byte load per particle; double4: two; the
 // mass rides along), velocities / accelerations / slab rows as real4 {·, ·, ·, 0}.
-// Kernels mirror the 2-D ones of nb_kernels.hip.h, in fp32 and fp64:
+// This file holds the 3-D force kernels and the gather of their slabs, in fp32 and fp64:
 //   force_sym3_f32 / _f64    symmetric (Newton's third law) fast path, lane-rotated travelling particles
 //   force_tiled3_f32 / _f64  one-sided LDS-tiled kernel (small n, eps = 0, all-gather sharding, cross-check);
 //                            the j range skips [gap_begin, gap_begin + gap_len) like the 2-D kernels
-//   sym_gather3 / integrate3 / pack3 / unpack3 / energy3 / (sum_partials of nb_kernels.hip.h)
+//   sym_gather3              sum of the symmetric slabs, one particle per thread
+// integrate, kick / drift, pack / unpack, energy, momentum and sum_partials are shared with 2-D: the kernels of
+// nb_kernels.hip.h keyed on Layout<real, true>.
 #pragma once
 #include "nb_kernels.hip.h"
 
 namespace nbk {
-
-template <typename real> struct vec4_of;
-template <> struct vec4_of<float> { typedef float4 type; };
-template <> struct vec4_of<double> { typedef double4 type; };
-
-template <typename real> __device__ __forceinline__ typename vec4_of<real>::type make_real4(real x, real y, real z, real w);
-template <> __device__ __forceinline__ float4 make_real4<float>(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
-template <> __device__ __forceinline__ double4 make_real4<double>(double x, double y, double z, double w) { return make_double4(x, y, z, w); }
-
-// ---------------------------------------------------------------------------
-// kick/drift for one particle, 3 components (the 2-D extras — velocity clamp, soft
-// boundary — are defined by the reference in the plane only and are not applied).
-// ---------------------------------------------------------------------------
-template <typename real>
-__device__ __forceinline__
-void kick_drift_one3(typename vec4_of<real>::type a, uint32_t li, const typename vec4_of<real>::type *__restrict__ pos_cur,
-                     typename vec4_of<real>::type *__restrict__ pos_next, typename vec4_of<real>::type *__restrict__ vel,
-                     typename vec4_of<real>::type *__restrict__ acc, uint32_t i_begin, real dt_kick, real dt_drift, int flags)
-{
-    typedef typename vec4_of<real>::type real4;
-    a.w = 0;
-    acc[li] = a;
-    if (!(flags & INTEG_KICK)) return;
-    real4 v = vel[li];
-    const real4 x = pos_cur[i_begin + li];
-    v.x = __builtin_fma(a.x, dt_kick, v.x);
-    v.y = __builtin_fma(a.y, dt_kick, v.y);
-    v.z = __builtin_fma(a.z, dt_kick, v.z);
-    vel[li] = v;
-    if (flags & INTEG_DRIFT) {
-        real4 xn;
-        xn.x = __builtin_fma(v.x, dt_drift, x.x);
-        xn.y = __builtin_fma(v.y, dt_drift, x.y);
-        xn.z = __builtin_fma(v.z, dt_drift, x.z);
-        xn.w = x.w;                                  // the mass travels with the position
-        pos_next[i_begin + li] = xn;
-    }
-}
-
-template <typename real>
-__global__ __launch_bounds__(BLOCK)
-void integrate3(const typename vec4_of<real>::type *__restrict__ pos_cur, typename vec4_of<real>::type *__restrict__ pos_next,
-                typename vec4_of<real>::type *__restrict__ vel, typename vec4_of<real>::type *__restrict__ acc,
-                const typename vec4_of<real>::type *__restrict__ partial, uint32_t nslabs,
-                uint32_t i_begin, uint32_t i_count, real dt_kick, real dt_drift, int flags)
-{
-    const uint32_t li = blockIdx.x * BLOCK + threadIdx.x;
-    if (li >= i_count) return;
-    auto a = partial[li];
-    for (uint32_t s = 1; s < nslabs; ++s) {
-        const auto b = partial[(size_t)s * i_count + li];
-        a.x += b.x; a.y += b.y; a.z += b.z;
-    }
-    kick_drift_one3<real>(a, li, pos_cur, pos_next, vel, acc, i_begin, dt_kick, dt_drift, flags);
-}
 
 // ---------------------------------------------------------------------------
 // force_tiled3_f32 — one-sided, LDS-tiled (the 3-D twin of force_tiled_f32, WS = 4).
@@ -620,128 +567,9 @@ void sym_gather3(const typename vec4_of<real>::type *__restrict__ slab_s, const 
 #pragma unroll
         for (int j = 1; j < GATHER_Q; ++j) { s.x += part[j][p].x; s.y += part[j][p].y; s.z += part[j][p].z; }
         if (base) { const real4 b = base[li]; s.x += b.x; s.y += b.y; s.z += b.z; }
-        if constexpr (FUSE) kick_drift_one3<real>(s, li, pos_cur, pos_next, vel, acc, k0, dt_kick, dt_drift, flags);
+        if constexpr (FUSE) kick_drift_one<Layout<real, true>, false>(s, li, pos_cur, pos_next, vel, acc, k0, dt_kick, dt_drift, 0, flags);
         else { s.w = 0; acc_sum[k] = s; }
     }
-}
-
-// ---------------------------------------------------------------------------
-// AoS (64-byte records, z in the first padding slot of pos / vel / acc) <-> SoA real4
-// ---------------------------------------------------------------------------
-template <typename real>
-__global__ __launch_bounds__(BLOCK)
-void unpack_bodies3(const BodyRec *__restrict__ aos, uint32_t n, typename vec4_of<real>::type *__restrict__ pos,
-                    typename vec4_of<real>::type *__restrict__ vel, typename vec4_of<real>::type *__restrict__ acc,
-                    float *__restrict__ radius, uint32_t i_begin, uint32_t i_count)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = aos[i].q[0], m = aos[i].q[3];
-    pos[i] = make_real4<real>((real)p.x, (real)p.y, (real)p.z, (real)m.x);
-    radius[i] = m.y;
-    if (i >= i_begin && i - i_begin < i_count) {
-        const float4 v = aos[i].q[1], a = aos[i].q[2];
-        vel[i - i_begin] = make_real4<real>((real)v.x, (real)v.y, (real)v.z, 0);
-        acc[i - i_begin] = make_real4<real>((real)a.x, (real)a.y, (real)a.z, 0);
-    }
-}
-
-template <typename real>
-__global__ __launch_bounds__(BLOCK)
-void pack_bodies3(BodyRec *__restrict__ aos, const typename vec4_of<real>::type *__restrict__ pos,
-                  const typename vec4_of<real>::type *__restrict__ vel, const typename vec4_of<real>::type *__restrict__ acc,
-                  const float *__restrict__ radius, uint32_t i_begin, uint32_t i_count)
-{
-    const uint32_t li = blockIdx.x * BLOCK + threadIdx.x;
-    if (li >= i_count) return;
-    const auto p = pos[i_begin + li], v = vel[li], a = acc[li];
-    BodyRec r;
-    r.q[0] = make_float4((float)p.x, (float)p.y, (float)p.z, 0.f);
-    r.q[1] = make_float4((float)v.x, (float)v.y, (float)v.z, 0.f);
-    r.q[2] = make_float4((float)a.x, (float)a.y, (float)a.z, 0.f);
-    r.q[3] = make_float4((float)p.w, radius[i_begin + li], 0.f, 0.f);
-    aos[li] = r;
-}
-
-// positions only, as packed (x, y, z) floats: the viewer's fast path in 3-D (12 bytes per body)
-template <typename real>
-__global__ __launch_bounds__(BLOCK)
-void pack_positions3(float *__restrict__ out, const typename vec4_of<real>::type *__restrict__ pos, uint32_t i_begin, uint32_t i_count)
-{
-    const uint32_t li = blockIdx.x * BLOCK + threadIdx.x;
-    if (li >= i_count) return;
-    const auto p = pos[i_begin + li];
-    out[3 * (size_t)li + 0] = (float)p.x;
-    out[3 * (size_t)li + 1] = (float)p.y;
-    out[3 * (size_t)li + 2] = (float)p.z;
-}
-
-// energy in fp64: K = sum m v^2 / 2, U = - sum_i m_i sum_{j > i} m_j / sqrt(r^2 + eps^2) (every unordered pair once)
-template <typename real>
-__global__ __launch_bounds__(BLOCK)
-void energy_partials3(const typename vec4_of<real>::type *__restrict__ pos, const typename vec4_of<real>::type *__restrict__ vel,
-                      uint32_t n, uint32_t i_begin, uint32_t i_count, double eps2, double *__restrict__ ksum, double *__restrict__ usum)
-{
-    struct alignas(16) JD { double x, y, z, m; };
-    __shared__ JD tile[TJ];
-    __shared__ double red[2][BLOCK / 64];
-    const uint32_t t = threadIdx.x, li = blockIdx.x * BLOCK + t;
-    const bool live = li < i_count;
-    const uint32_t gi = i_begin + (live ? li : i_count - 1);
-    const auto pi = pos[gi];
-    const double xi = pi.x, yi = pi.y, zi = pi.z;
-    const double k0375 = vgpr_const(0.375);
-    double u = 0.0;
-    const uint32_t first = ((i_begin + blockIdx.x * BLOCK) / TJ) * TJ;
-    for (uint32_t j0 = first; j0 < n; j0 += TJ) {
-        const uint32_t j = j0 + t;
-        __syncthreads();
-        if (j < n) { const auto q = pos[j]; tile[t] = JD{(double)q.x, (double)q.y, (double)q.z, (double)q.w}; }
-        else tile[t] = JD{0.0, 0.0, 0.0, 0.0};
-        __syncthreads();
-        const uint32_t cnt = min((uint32_t)TJ, n - j0);
-        for (uint32_t jj = 0; jj < cnt; ++jj) {
-            const double dx = tile[jj].x - xi, dy = tile[jj].y - yi, dz = tile[jj].z - zi;
-            const double r2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2)));
-            const double wgt = (j0 + jj > gi) ? tile[jj].m : 0.0;
-            u = __builtin_fma(wgt, rsqrt_f64(r2, k0375), u);
-        }
-    }
-    double k = 0.0, uu = 0.0;
-    if (live) {
-        const double m = (double)pi.w;
-        const auto v = vel[li];
-        k = 0.5 * m * ((double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z);
-        uu = -m * u;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { k += __shfl_down(k, off, 64); uu += __shfl_down(uu, off, 64); }
-    if ((t & 63) == 0) { red[0][t >> 6] = k; red[1][t >> 6] = uu; }
-    __syncthreads();
-    if (t == 0) {
-        double ks = 0.0, us = 0.0;
-        for (int wv = 0; wv < BLOCK / 64; ++wv) { ks += red[0][wv]; us += red[1][wv]; }
-        ksum[blockIdx.x] = ks;
-        usum[blockIdx.x] = us;
-    }
-}
-
-// momentum of the owned block (see momentum_partials): px | py | pz | Lz (z component of x cross m v)
-template <typename real>
-__global__ __launch_bounds__(BLOCK)
-void momentum_partials3(const typename vec4_of<real>::type *__restrict__ pos, const typename vec4_of<real>::type *__restrict__ vel,
-                        uint32_t i_begin, uint32_t i_count, double *__restrict__ psum)
-{
-    const uint32_t li = blockIdx.x * BLOCK + threadIdx.x;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    if (li < i_count) {
-        const auto p = pos[i_begin + li];
-        const auto w = vel[li];
-        const double m = (double)p.w;
-        v[0] = m * (double)w.x; v[1] = m * (double)w.y; v[2] = m * (double)w.z;
-        v[3] = m * ((double)p.x * (double)w.y - (double)p.y * (double)w.x);
-    }
-    block_reduce4(v, psum, gridDim.x);
 }
 
 } // namespace nbk
