@@ -33,7 +33,7 @@ extern "C" {
  * nb_* symbols; tests/test_abi.py).  Test hooks live in include/nbody_debug.h and exist only in a -DNB_TEST_HOOKS build. */
 #pragma GCC visibility push(default)
 
-#define NB_ABI_VERSION 6
+#define NB_ABI_VERSION 7
 
 /* ---- particle record -------------------------------------------------------
  * Bit-compatible with the reference's `struct alignas(16) Body`
@@ -95,7 +95,19 @@ enum { NB_SUM_TILED = 0,       /* LDS-tiled, packed FP32, FMA-contracted: fast p
 
 /* nb_params.extras bit flags: the non-gravity parts of Simulation::iterate */
 enum { NB_EXTRA_VCLAMP   = 1,   /* |v| <= 1000,            Simulation.hpp:133-137 */
-       NB_EXTRA_BOUNDARY = 2 }; /* soft boundary + damping, Simulation.hpp:140-155 */
+       NB_EXTRA_BOUNDARY = 2,   /* soft boundary + damping, Simulation.hpp:140-155 */
+       NB_EXTRA_COLLIDE  = 4 }; /* hard-sphere collisions after the drift, collide() / resolve(), Simulation.hpp:216-346 (ABI 7).
+                                   Each step then ends with: P = every pair i < j whose discs overlap at the drifted positions
+                                   (d = p_j - p_i, d.x*d.x + d.y*d.y <= (r_i + r_j)^2, one rounding per operation; coincident
+                                   bodies count, radius 0 included), fixed first; then the reference's resolve(i, j) once per pair
+                                   of P in ascending (i, j) order, each on the current state of both bodies.  acc is untouched.
+                                   Unsharded 2-D kick-drift handles only (nb_create: NB_EINVAL otherwise).  Where no body is in
+                                   two pairs and each pair lies in one of the reference's 600-unit cells, the result is the
+                                   reference's own step() bit for bit (INTEGRATION.md §2 has the differences otherwise).
+                                   Pair capacity: max(8 n, 65536) pairs; a step with more resolves nothing, and the next
+                                   synchronising call (nb_wait, nb_sync, nb_sync_positions, nb_snapshot_wait, nb_energy,
+                                   nb_momentum, nb_collision_stats) returns NB_ENOMEM once, naming the frame and the pairs
+                                   needed; nb_collide_capacity raises it */
 
 /* integrator */
 enum { NB_INTEGRATOR_KICK_DRIFT = 0, /* Simulation.hpp:129-131,160-163 (reference) */
@@ -219,8 +231,8 @@ void nb_destroy(nb_sim *s);
  * time step dt (dt <= 0 -> params.dt; the reference reads the global
  * SIMULATION_DT once per step, Simulation.hpp:69).  Each step = force
  * evaluation at x_n (attract, :176) -> v += a dt -> x += v dt (iterate,
- * :129-163), ++frame (:74).  collide() (:72) is NOT performed: it is not
- * gravity and is a no-op for radius-0 bodies.  Work is ENQUEUED on
+ * :129-163), ++frame (:74).  collide() (:72) is performed only with
+ * NB_EXTRA_COLLIDE (off by default: it is not gravity).  Work is ENQUEUED on
  * the handle's stream; nb_wait / nb_sync / nb_energy order after it. */
 int nb_step(nb_sim *s, float dt, int nsteps);
 
@@ -288,6 +300,14 @@ int nb_energy(nb_sim *s, double *kinetic, double *potential);
  * accumulation on the device in a fixed order.  Both are conserved by the pairwise force (Newton's third law) up to
  * rounding, whatever the softening; a sharded handle returns its owned block's share (the shares add up). */
 int nb_momentum(nb_sim *s, double *p_xyz, double *l_z);
+
+/* Collisions (NB_EXTRA_COLLIDE).  nb_collide_capacity sets the pair capacity (1 .. 2^31 - 1) between steps; NB_ESTATE on a
+ * handle created without the bit.  nb_collision_stats synchronises and returns the pairs of the last step, the pairs resolved
+ * since creation, the resolution rounds of the last step (ready pairs are resolved together; a chain of k touching discs
+ * costs k - 1 rounds) and the steps that were over capacity; any pointer may be NULL; all zero without the bit. */
+int nb_collide_capacity(nb_sim *s, size_t max_pairs);
+int nb_collision_stats(nb_sim *s, uint64_t *pairs_last_step, uint64_t *pairs_total, uint32_t *rounds_last_step,
+                       uint64_t *overflow_steps);
 
 /* Counters: Simulation::frame (Simulation.hpp:53) and sizes. */
 uint64_t nb_frame(const nb_sim *s);

@@ -17,14 +17,14 @@ import numpy as np
 PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = PKG_DIR / "libnbody_hip.so"
 
-NB_ABI_VERSION = 6
+NB_ABI_VERSION = 7
 
 # enums (include/nbody.h)
 NB_OK, NB_EINVAL, NB_ENODEVICE, NB_EHIP, NB_ENOMEM, NB_EIO, NB_EFORMAT, NB_ESTATE = 0, -1, -2, -3, -4, -5, -6, -7
 NB_FP32, NB_FP64 = 0, 1
 NB_RSQRT_EXACT, NB_RSQRT_QUAKE = 0, 1
 NB_SUM_TILED, NB_SUM_SEQUENTIAL = 0, 1
-NB_EXTRA_VCLAMP, NB_EXTRA_BOUNDARY = 1, 2
+NB_EXTRA_VCLAMP, NB_EXTRA_BOUNDARY, NB_EXTRA_COLLIDE = 1, 2, 4
 NB_INTEGRATOR_KICK_DRIFT, NB_INTEGRATOR_KDK = 0, 1
 NB_POS_CURRENT, NB_POS_NEXT = 0, 1
 NB_SHARD_NONE, NB_SHARD_ALLGATHER, NB_SHARD_SYMMETRIC, NB_SHARD_ALLREDUCE = 0, 1, 2, 3
@@ -163,6 +163,8 @@ PROTOTYPES = {
     "nb_accelerations": (C.c_int, [C.c_void_p]),
     "nb_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nb_momentum": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "nb_collide_capacity": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "nb_collision_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),
     "nb_owned_begin": (C.c_size_t, [C.c_void_p]),

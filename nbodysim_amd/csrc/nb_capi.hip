@@ -11,6 +11,7 @@
 #include "nb_internal.h"
 #include "nb_kernels.hip.h"
 #include "nb_kernels3d.hip.h"
+#include "nb_collide.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -146,6 +147,28 @@ struct nb_sim {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_late = nullptr;
     hipEvent_t ev_x[2] = {nullptr, nullptr};   // in-process exchanges: fences between the handles' streams
     uint64_t peers_enabled = 0;                // devices whose memory this handle's device has mapped
+
+    // hard-sphere collisions (NB_EXTRA_COLLIDE, nb_collide.hip.h): nothing below is allocated when the bit is off
+    bool collide = false;
+    double coll_h = 0.0;                       // grid cell size: a little over twice the largest small radius
+    uint32_t coll_large_n = 0;                 // large bodies (tested against all n), <= COLLIDE_MAX_LARGE
+    uint32_t coll_slots = 0;                   // cell table slots (power of two >= 2n)
+    uint32_t coll_words = 0;                   // 32-body words of one large body's bitmap
+    uint64_t coll_cap = 0;                     // pair capacity
+    uint64_t coll_ovf_reported = 0;            // overflow steps already reported by a synchronising call
+    uint8_t *coll_large = nullptr;             // n flags: 1 = large body
+    uint32_t *coll_large_list = nullptr;       // COLLIDE_MAX_LARGE body indices
+    int *coll_head = nullptr, *coll_next = nullptr;
+    int2 *coll_cell = nullptr;
+    uint32_t *coll_deg = nullptr, *coll_off = nullptr, *coll_tidx = nullptr, *coll_tlist = nullptr;
+    uint32_t *coll_adj = nullptr, *coll_bits = nullptr;
+    uint64_t *coll_chunk_e = nullptr;           // the scan's per-chunk sums / prefixes (collide_scan_*)
+    uint32_t *coll_chunk_t = nullptr;
+    void *coll_spos = nullptr, *coll_svel = nullptr;   // global-memory resolution: touched bodies' state
+    uint32_t *coll_scur = nullptr;
+    uint8_t *coll_sadv = nullptr;
+    CollideStats *coll_stats = nullptr;        // device
+    CollideStats *coll_host = nullptr;         // page-locked mirror
 
     // profiling
     bool prof = false;
@@ -634,6 +657,11 @@ static void free_all(nb_sim *s)
     if (s->own_acc) { (void)hipFree(s->acc_full); (void)hipFree(s->acc_owned); }
     (void)hipFree(s->sym_slab_s); (void)hipFree(s->sym_slab_r);
     (void)hipFree(s->sym_ticket);
+    for (void *q : {(void *)s->coll_large, (void *)s->coll_large_list, (void *)s->coll_head, (void *)s->coll_next, (void *)s->coll_cell,
+                    (void *)s->coll_deg, (void *)s->coll_off, (void *)s->coll_tidx, (void *)s->coll_tlist, (void *)s->coll_adj,
+                    (void *)s->coll_bits, (void *)s->coll_chunk_e, (void *)s->coll_chunk_t, s->coll_spos, s->coll_svel, (void *)s->coll_scur, (void *)s->coll_sadv, (void *)s->coll_stats})
+        (void)hipFree(q);
+    if (s->coll_host) (void)hipHostFree(s->coll_host);
     if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
     if (s->ev_packed) (void)hipEventDestroy(s->ev_packed);
     if (s->ev_copied) (void)hipEventDestroy(s->ev_copied);
@@ -722,6 +750,153 @@ static int fence_foreign_work(nb_sim *s)
     return NB_OK;
 }
 
+// ---------------------------------------------------------------------------
+// collisions (NB_EXTRA_COLLIDE): host side of nb_collide.hip.h
+// ---------------------------------------------------------------------------
+static int collide_alloc_pairs(nb_sim *s, uint64_t cap)
+{
+    (void)hipFree(s->coll_adj);
+    s->coll_adj = nullptr;
+    s->coll_cap = 0;
+    HIPCHK(hipMalloc((void **)&s->coll_adj, 2 * cap * sizeof(uint32_t)));    // every pair sits in two rows
+    s->coll_cap = cap;
+    return NB_OK;
+}
+
+// Everything the collision path needs, sized by n once (nb_create): radii never change on the device.
+static int collide_alloc(nb_sim *s)
+{
+    const size_t n = s->n;
+    uint32_t slots = 1024;
+    while (slots < 2 * n) slots <<= 1;
+    s->coll_slots = slots;
+    s->coll_words = (uint32_t)((n + 31) / 32);
+    HIPCHK(hipMalloc((void **)&s->coll_large, n));
+    HIPCHK(hipMalloc((void **)&s->coll_large_list, COLLIDE_MAX_LARGE * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->coll_head, slots * sizeof(int)));
+    HIPCHK(hipMalloc((void **)&s->coll_next, n * sizeof(int)));
+    HIPCHK(hipMalloc((void **)&s->coll_cell, n * sizeof(int2)));
+    HIPCHK(hipMalloc((void **)&s->coll_deg, n * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->coll_off, (n + 1) * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->coll_tidx, n * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->coll_tlist, n * sizeof(uint32_t)));
+    const size_t chunks = (n + COLLIDE_SCAN_CHUNK - 1) / COLLIDE_SCAN_CHUNK;
+    HIPCHK(hipMalloc((void **)&s->coll_chunk_e, chunks * sizeof(uint64_t)));
+    HIPCHK(hipMalloc((void **)&s->coll_chunk_t, chunks * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->coll_bits, (size_t)COLLIDE_MAX_LARGE * s->coll_words * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&s->coll_spos, n * s->esz));
+    HIPCHK(hipMalloc(&s->coll_svel, n * s->esz));
+    HIPCHK(hipMalloc((void **)&s->coll_scur, n * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->coll_sadv, n));
+    HIPCHK(hipMalloc((void **)&s->coll_stats, sizeof(CollideStats)));
+    HIPCHK(hipHostMalloc((void **)&s->coll_host, sizeof(CollideStats), hipHostMallocDefault));
+    HIPCHK(hipMemsetAsync(s->coll_stats, 0, sizeof(CollideStats), s->stream));
+    memset(s->coll_host, 0, sizeof(CollideStats));
+    const uint64_t cap = std::max<uint64_t>(8 * (uint64_t)n, 65536);
+    return collide_alloc_pairs(s, cap);
+}
+
+// Size classes of the uploaded radii (magnitudes: the predicate squares r_i + r_j): r_q = the 99th percentile; bodies above
+// 2 r_q are LARGE (at most COLLIDE_MAX_LARGE, else there is no large set) and are tested against all n; the grid cell is
+// h = 2 x the largest small radius, raised by 2^-16 relative so that no pair the rounded predicate accepts (a few ulps past
+// r_i + r_j) or the rounded cell quotient places can lie beyond the neighbouring cell.
+static int collide_classify(nb_sim *s, const nb_body *in)
+{
+    const size_t n = s->n;
+    std::vector<float> r(n);
+    for (size_t i = 0; i < n; ++i) r[i] = std::fabs(in[i].radius);
+    std::vector<float> sorted(r);
+    const size_t q = (size_t)(0.99 * (double)(n - 1));
+    std::nth_element(sorted.begin(), sorted.begin() + (long)q, sorted.end(),
+                     [](float a, float b) { return a < b || (a == a && b != b); });   // NaN last
+    const float rq = sorted[q];
+    std::vector<uint8_t> large(n, 0);
+    std::vector<uint32_t> list;
+    for (size_t i = 0; i < n; ++i)
+        if (r[i] > 2.0f * rq) { large[i] = 1; list.push_back((uint32_t)i); }
+    if (list.size() > COLLIDE_MAX_LARGE) { std::fill(large.begin(), large.end(), 0); list.clear(); }
+    double rmax = 0.0;
+    for (size_t i = 0; i < n; ++i)
+        if (!large[i] && r[i] == r[i]) rmax = std::max(rmax, (double)r[i]);
+    s->coll_h = rmax > 0.0 ? 2.0 * rmax * (1.0 + 0x1p-16) : 1.0;      // radii all 0: only coincident bodies meet, any cell does
+    s->coll_large_n = (uint32_t)list.size();
+    { const int rc = copy_h2d(s, s->coll_large, large.data(), n); if (rc) return rc; }
+    if (!list.empty()) { const int rc = copy_h2d(s, s->coll_large_list, list.data(), list.size() * sizeof(uint32_t)); if (rc) return rc; }
+    return NB_OK;
+}
+
+// The collision pass of one step, on the post-drift state pos[cur] / vel (nb_collide.hip.h): `frame` is the frame it ends.
+static int launch_collide(nb_sim *s)
+{
+    const uint32_t n = (uint32_t)s->n, g = (n + BLOCK - 1) / BLOCK;
+    const uint32_t gc = std::min<uint32_t>((std::max(s->coll_slots, n) + BLOCK - 1) / BLOCK, 4096);
+    const double inv_h = std::isfinite(s->coll_h) ? 1.0 / s->coll_h : 0.0;   // an infinite radius: one cell holds everybody
+    const uint32_t mask = s->coll_slots - 1;
+    collide_clear<<<gc, BLOCK, 0, s->stream>>>(s->coll_head, s->coll_slots, s->coll_deg, n);
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        if constexpr (!L.dims3) {
+            vec *pos = (vec *)s->pos[s->cur], *vel = (vec *)s->vel;
+            collide_hash<vec><<<g, BLOCK, 0, s->stream>>>(pos, n, s->coll_large, inv_h, mask, s->coll_head, s->coll_next, s->coll_cell);
+            collide_rows<vec, false><<<g, BLOCK, 0, s->stream>>>(pos, s->radius, n, s->coll_large, s->coll_large_list, s->coll_large_n, mask,
+                                                                 s->coll_head, s->coll_next, s->coll_cell, s->coll_deg, nullptr, nullptr,
+                                                                 nullptr, s->coll_stats);
+            if (s->coll_large_n)
+                collide_large_bits<vec><<<dim3((s->coll_words + BLOCK - 1) / BLOCK, s->coll_large_n), BLOCK, 0, s->stream>>>(
+                    pos, s->radius, n, s->coll_large_list, s->coll_words, s->coll_bits, s->coll_deg);
+            const uint32_t chunks = (n + COLLIDE_SCAN_CHUNK - 1) / COLLIDE_SCAN_CHUNK;
+            collide_scan_blocks<<<chunks, BLOCK, 0, s->stream>>>(s->coll_deg, n, s->coll_chunk_e, s->coll_chunk_t);
+            collide_scan_top<<<1, BLOCK, 0, s->stream>>>(s->coll_chunk_e, s->coll_chunk_t, chunks, n, s->coll_off, s->coll_stats, s->coll_cap,
+                                                         s->frame);
+            collide_scan_fill<<<chunks, BLOCK, 0, s->stream>>>(s->coll_deg, n, s->coll_chunk_e, s->coll_chunk_t, s->coll_off, s->coll_tidx,
+                                                               s->coll_tlist, s->coll_stats);
+            collide_rows<vec, true><<<g, BLOCK, 0, s->stream>>>(pos, s->radius, n, s->coll_large, s->coll_large_list, s->coll_large_n, mask,
+                                                                s->coll_head, s->coll_next, s->coll_cell, nullptr, s->coll_off, s->coll_tidx,
+                                                                s->coll_adj, s->coll_stats);
+            if (s->coll_large_n)
+                collide_large_fill<<<s->coll_large_n, BLOCK, 0, s->stream>>>(s->coll_bits, s->coll_words, s->coll_large_list, s->coll_off,
+                                                                             s->coll_tidx, s->coll_adj, s->coll_stats);
+            collide_resolve<real, vec><<<1, COLLIDE_THREADS, 0, s->stream>>>(pos, vel, (const real *)s->mass, s->radius, s->coll_off,
+                                                                              s->coll_tlist, s->coll_adj, s->coll_stats, (vec *)s->coll_spos,
+                                                                              (vec *)s->coll_svel, s->coll_scur, s->coll_sadv);
+        }
+    });
+    HIPCHK(hipGetLastError());
+    return NB_OK;
+}
+
+// Reads the device record (waits for the handle's stream).  A step over capacity is reported ONCE, by the first synchronising
+// call after it: NB_ENOMEM naming the frame, the pairs needed and the capacity.
+static int collide_read(nb_sim *s)
+{
+    HIPCHK(hipMemcpyAsync(s->coll_host, s->coll_stats, sizeof(CollideStats), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return NB_OK;
+}
+
+// the report itself, from the host mirror as last read
+static int collide_report(nb_sim *s)
+{
+    if (!s->collide) return NB_OK;
+    const CollideStats &c = *s->coll_host;
+    if (c.overflow_steps <= s->coll_ovf_reported) return NB_OK;
+    const unsigned long long steps = (unsigned long long)(c.overflow_steps - s->coll_ovf_reported);
+    s->coll_ovf_reported = c.overflow_steps;
+    return nb_fail(NB_ENOMEM, "collisions: the step ending at frame %llu found %llu overlapping pairs, more than the capacity of %llu, "
+                              "and resolved none (%llu step(s) over capacity since the last report); raise it with nb_collide_capacity",
+                   (unsigned long long)c.overflow_frame, (unsigned long long)c.overflow_needed, (unsigned long long)s->coll_cap, steps);
+}
+
+static int collide_check(nb_sim *s)
+{
+    if (!s->collide) return NB_OK;
+    const int rc = collide_read(s);
+    return rc ? rc : collide_report(s);
+}
+
+static int snapshot_wait(nb_sim *s);
+
 static int do_upload(nb_sim *s, const nb_body *in)
 {
     { const int rc = fence_foreign_work(s); if (rc) return rc; }
@@ -775,6 +950,7 @@ static int do_upload(nb_sim *s, const nb_body *in)
         HIPCHK(hipGetLastError());
     }
     s->mass_scaled = forced_scaling;
+    if (s->collide) { const int rc = collide_classify(s, in); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(s->stream));  // `in` may be pageable and freed by the caller
     s->acc_valid = false;
     if (auto_scaling) { const int rc = choose_mass_scaling(s); if (rc) return rc; }
@@ -809,7 +985,15 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
         return nullptr;
     }
     if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
-    if (p.extras & ~(NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY)) { nb_set_error("nb_create: unknown bits in extras 0x%x", (unsigned)p.extras); return nullptr; }
+    if (p.extras & ~(NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY | NB_EXTRA_COLLIDE)) { nb_set_error("nb_create: unknown bits in extras 0x%x", (unsigned)p.extras); return nullptr; }
+    if (p.extras & NB_EXTRA_COLLIDE) {
+        const char *why = p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
+                        : p.shard_world > 1 ? "shard_world > 1" : (p.i_count != 0 && p.i_count < n) ? "i_count < n" : (p.flags & NB_FLAG_SHARD_SINGLE) ? "NB_FLAG_SHARD_SINGLE" : nullptr;
+        if (why) {
+            nb_set_error("nb_create: collisions (NB_EXTRA_COLLIDE) need an unsharded 2-D kick-drift handle; not supported with %s", why);
+            return nullptr;
+        }
+    }
     if (p.sym_chunks_per_item < 0 || p.sym_aux_stream < -1 || p.sym_aux_stream > 1 || p.j_slices < 0 || p.sym_chunk_pairs < -1 || p.sym_chunk_pairs > 1 ||
         (p.sym_tile != 0 && p.sym_tile != (int32_t)SYM_SB_WS && p.sym_tile != (int32_t)SYM_SB) ||
         (p.lanes_p != 0 && p.lanes_p != 1 && p.lanes_p != 2 && p.lanes_p != 4) || !(p.sym_late_us == p.sym_late_us)) {
@@ -892,6 +1076,8 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     if ((e = hipMalloc((void **)&s->ered_dev, 2 * s->ered_blocks * sizeof(double))) != hipSuccess) return fail("hipMalloc energy", e);
 
     if (symmetric(s) && plan_sym(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
+    s->collide = (p.extras & NB_EXTRA_COLLIDE) != 0;
+    if (s->collide && collide_alloc(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
     if (do_upload(s, init) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
     return s;
 }
@@ -902,7 +1088,7 @@ extern "C" int nb_upload(nb_sim *s, const nb_body *in)
 {
     if (!s || !in) return nb_fail(NB_EINVAL, "nb_upload: NULL argument");
     if (bind(s)) return NB_EHIP;
-    if (nb_snapshot_wait(s)) return nb_last_error_code();      // the AoS staging array may still feed a pipelined snapshot
+    if (snapshot_wait(s)) return nb_last_error_code();         // the AoS staging array may still feed a pipelined snapshot
     return do_upload(s, in);
 }
 
@@ -1275,6 +1461,9 @@ extern "C" int nb_step_finish(nb_sim *s)
     s->cur ^= 1;
     s->frame += 1;                                  // Simulation.hpp:74
     s->acc_valid = false;
+    // Simulation.hpp:72: collide() after iterate(), on the drifted positions (the frame counter is host-side: the order of
+    // the two lines above and this launch is not observable)
+    if (s->collide && (rc = launch_collide(s))) return rc;
     return NB_OK;
 }
 
@@ -1334,7 +1523,7 @@ extern "C" int nb_wait(nb_sim *s)
     if (bind(s)) return NB_EHIP;
     if (s->aux) HIPCHK(hipStreamSynchronize(s->aux));
     HIPCHK(hipStreamSynchronize(s->stream));
-    return NB_OK;
+    return collide_check(s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1430,9 +1619,8 @@ static int launch_pack_range(nb_sim *s, BodyRec *out, uint32_t o, uint32_t cnt)
 
 static int launch_pack(nb_sim *s) { return launch_pack_range(s, s->aos_dev, 0, (uint32_t)s->i_count); }
 
-extern "C" int nb_snapshot_wait(nb_sim *s)
+static int snapshot_wait(nb_sim *s)
 {
-    if (!s) return nb_fail(NB_EINVAL, "nb_snapshot_wait: NULL handle");
     if (!s->snap_pending) return NB_OK;
     if (bind(s)) return NB_EHIP;
     HIPCHK(hipEventSynchronize(s->ev_copied));
@@ -1440,6 +1628,13 @@ extern "C" int nb_snapshot_wait(nb_sim *s)
     s->snap_pending = false;
     s->snap_out = nullptr;
     return NB_OK;
+}
+
+extern "C" int nb_snapshot_wait(nb_sim *s)
+{
+    if (!s) return nb_fail(NB_EINVAL, "nb_snapshot_wait: NULL handle");
+    const int rc = snapshot_wait(s);
+    return rc ? rc : collide_report(s);        // the record nb_snapshot_begin copied beside the bodies: no wait for later steps
 }
 
 extern "C" int nb_snapshot_begin(nb_sim *s, nb_body *out)
@@ -1458,6 +1653,7 @@ extern "C" int nb_snapshot_begin(nb_sim *s, nb_body *out)
     // aos_dev is free again: the previous snapshot was waited for, and nb_sync / nb_upload synchronise before returning
     int rc = launch_pack(s);
     if (rc) return rc;
+    if (s->collide) HIPCHK(hipMemcpyAsync(s->coll_host, s->coll_stats, sizeof(CollideStats), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipEventRecord(s->ev_packed, s->stream));
     HIPCHK(hipStreamWaitEvent(s->copy_stream, s->ev_packed, 0));
     HIPCHK(hipMemcpyAsync(s->snap_direct ? (void *)out : s->staging, s->aos_dev, s->i_count * sizeof(nb_body), hipMemcpyDeviceToHost, s->copy_stream));
@@ -1471,8 +1667,8 @@ extern "C" int nb_sync(nb_sim *s, nb_body *out)
 {
     if (!s || !out) return nb_fail(NB_EINVAL, "nb_sync: NULL argument");
     if (bind(s)) return NB_EHIP;
-    int rc = nb_snapshot_wait(s);                     // aos_dev / staging may still be feeding a pipelined snapshot
-    if (rc) return rc;
+    int rc = snapshot_wait(s);                        // aos_dev / staging may still be feeding a pipelined snapshot
+    if (rc || (rc = collide_check(s))) return rc;
     const size_t bytes = s->i_count * sizeof(nb_body);
     const bool direct = pinned_covers(out, bytes);
     if (!direct && ensure_staging(s)) return NB_EHIP;
@@ -1505,7 +1701,8 @@ extern "C" int nb_sync_positions(nb_sim *s, float *out_xy)
 {
     if (!s || !out_xy) return nb_fail(NB_EINVAL, "nb_sync_positions: NULL argument");
     if (bind(s)) return NB_EHIP;
-    if (nb_snapshot_wait(s)) return nb_last_error_code();
+    if (snapshot_wait(s)) return nb_last_error_code();
+    { const int rc = collide_check(s); if (rc) return rc; }
     if (ensure_staging(s)) return NB_EHIP;
     const uint32_t ic = (uint32_t)s->i_count, g = (ic + BLOCK - 1) / BLOCK;
     const size_t bytes = s->i_count * (s->dims3 ? 3 : 2) * sizeof(float);       // (x, y) or (x, y, z) per body
@@ -1527,6 +1724,7 @@ extern "C" int nb_energy(nb_sim *s, double *kinetic, double *potential)
 {
     if (!s || !kinetic || !potential) return nb_fail(NB_EINVAL, "nb_energy: NULL argument");
     if (bind(s)) return NB_EHIP;
+    { const int rc = collide_check(s); if (rc) return rc; }
     const uint32_t g = (uint32_t)s->ered_blocks;
     const double eps2 = (double)s->p.eps * (double)s->p.eps;
     with_layout(s, [&](auto L) {
@@ -1550,6 +1748,7 @@ extern "C" int nb_momentum(nb_sim *s, double *p_xyz, double *l_z)
 {
     if (!s || !p_xyz) return nb_fail(NB_EINVAL, "nb_momentum: NULL argument");
     if (bind(s)) return NB_EHIP;
+    { const int rc = collide_check(s); if (rc) return rc; }
     const uint32_t g = (uint32_t)s->ered_blocks;
     if (!s->pred_dev) HIPCHK(hipMalloc((void **)&s->pred_dev, 4 * (size_t)g * sizeof(double)));
     with_layout(s, [&](auto L) {
@@ -1568,6 +1767,36 @@ extern "C" int nb_momentum(nb_sim *s, double *p_xyz, double *l_z)
     p_xyz[0] = acc[0]; p_xyz[1] = acc[1]; p_xyz[2] = acc[2];
     if (l_z) *l_z = acc[3];
     return NB_OK;
+}
+
+extern "C" int nb_collide_capacity(nb_sim *s, size_t max_pairs)
+{
+    if (!s) return nb_fail(NB_EINVAL, "nb_collide_capacity: NULL handle");
+    if (!s->collide) return nb_fail(NB_ESTATE, "nb_collide_capacity: the handle was created without NB_EXTRA_COLLIDE");
+    if (max_pairs == 0 || max_pairs > 0x7fffffffu) return nb_fail(NB_EINVAL, "nb_collide_capacity: max_pairs must be 1 .. 2^31 - 1");
+    if (s->in_step) return nb_fail(NB_ESTATE, "nb_collide_capacity: a split step is in flight");
+    if (bind(s)) return NB_EHIP;
+    HIPCHK(hipStreamSynchronize(s->stream));          // the pair rows of the steps enqueued so far
+    return collide_alloc_pairs(s, max_pairs);
+}
+
+extern "C" int nb_collision_stats(nb_sim *s, uint64_t *pairs_last_step, uint64_t *pairs_total, uint32_t *rounds_last_step,
+                                  uint64_t *overflow_steps)
+{
+    if (!s) return nb_fail(NB_EINVAL, "nb_collision_stats: NULL handle");
+    if (bind(s)) return NB_EHIP;
+    CollideStats c{};
+    int rc = NB_OK;
+    if (s->collide) {
+        rc = collide_check(s);
+        c = *s->coll_host;
+        if (rc && nb_last_error_code() != NB_ENOMEM) return rc;
+    }
+    if (pairs_last_step) *pairs_last_step = c.pairs_last;
+    if (pairs_total) *pairs_total = c.pairs_total;
+    if (rounds_last_step) *rounds_last_step = c.rounds_last;
+    if (overflow_steps) *overflow_steps = c.overflow_steps;
+    return rc;
 }
 
 extern "C" uint64_t nb_frame(const nb_sim *s) { return s ? s->frame : 0; }
@@ -1819,7 +2048,12 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
     if (!s || !buf || !buflen) return nb_fail(NB_EINVAL, "nb_describe: NULL argument");
     const ForceJob &a = s->job_all;
     const bool seq = s->p.sum_order == NB_SUM_SEQUENTIAL;
-    snprintf(buf, buflen,
+    const char *resolve = "none";
+    if (s->collide) {
+        if (bind(s) || collide_read(s)) return nb_last_error_code();     // the last step's record (an overflow stays unreported)
+        resolve = s->coll_host->touched == 0 ? "none" : s->coll_host->lds_last ? "lds" : "global";
+    }
+    const int used = snprintf(buf, buflen,
              "n=%zu owned=[%zu,+%zu) %s%s rsqrt=%s sum=%s | force: block=%d waves/i-set=%d i/lane=%d i_tiles=%u j_slices(all)=%u grid=%u tile_j=%d | "
              "two-phase P/slices local=%d/%u remote=%d/%u | uniform_mass=%d mass_scaled=%d mass_scaling_check=%.1e | symmetric=%d tile=%u chunk_pairs=%d items=%u chunks/item=%u late=%u slabs=%.1f+%.1f MiB | CUs=%d",
              s->n, s->i_begin, s->i_count, s->fp64 ? "fp64" : "fp32", s->dims3 ? " 3-D" : "",
@@ -1829,5 +2063,8 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
              s->job_local.P, s->job_local.js, s->job_remote.P, s->job_remote.js, (int)s->uniform_mass, (int)s->mass_scaled, (double)s->mass_scaling_dev,
              (int)symmetric(s), s->sym_sb, (int)sym_uses_pairs(s), s->sym_items, s->sym_L, s->sym_items_late,
              (double)s->sym_info.slab_s_bytes / 1048576.0, (double)s->sym_info.slab_r_bytes / 1048576.0, s->cus);
+    if (used >= 0 && (size_t)used < buflen)
+        snprintf(buf + used, buflen - (size_t)used, " | collide=%d h=%.6g large=%u capacity=%llu resolve=%s", (int)s->collide, s->coll_h,
+                 s->coll_large_n, (unsigned long long)s->coll_cap, resolve);
     return NB_OK;
 }

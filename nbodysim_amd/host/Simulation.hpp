@@ -18,9 +18,11 @@
 //
 // `Simulation()` starts, like the reference's, from uniform_disc(25000) with epsilon = 1 and the velocity
 // clamp + soft boundary of iterate() switched on; a second constructor takes any initial bodies.
-// Differences, all deliberate: the force is the direct O(N^2) sum, not Barnes-Hut, and
+// Differences, all deliberate: the force is the direct O(N^2) sum, not Barnes-Hut, and by default
 // collide() (Simulation.hpp:72,216-346) is NOT run — bodies with radius > 0 pass through each other, so a run
-// from `Simulation()` follows the reference's gravity + clamp + boundary, not its collisions.
+// from `Simulation()` follows the reference's gravity + clamp + boundary, not its collisions.  Built with
+// -DNBODY_COLLIDE=1, reference_params() adds NB_EXTRA_COLLIDE and step() ends with the library's restatement of
+// collide() (the pair order and the once-per-pair rule differ from the reference's spatial hash).
 #pragma once
 #include <atomic>
 #include <cmath>
@@ -183,6 +185,9 @@ private:
         static nb_params p;
         nb_params_default(&p);
         p.extras = NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY;     // Simulation.hpp:133-155
+#if defined(NBODY_COLLIDE) && NBODY_COLLIDE
+        p.extras |= NB_EXTRA_COLLIDE;                       // Simulation.hpp:72,216-346
+#endif
         return &p;
     }
     static void check(int rc, const char *what)

@@ -9,6 +9,7 @@
  *              [-sequential] [-kdk] [-dump FILE] [-load FILE] [-sync-every K]
  *              [-reference-ics]  the reference's own start: Simulation()'s 25 000-body disc (or -n N of it),
  *                            eps = 1, dt = 0.01, velocity clamp + soft boundary (Simulation.hpp:58-65,116-163)
+ *              [-collide]    end every step with the reference's hard-sphere collisions (NB_EXTRA_COLLIDE, Simulation.hpp:216-346)
  *              [-shards P]   P sharded handles driven from this one process (device r mod #GPUs),
  *                            exchanged with nb_exchange_positions: multi-GPU without RCCL
  *              [-no-symmetry] one-sided kernels / all-gather protocol (nb_params.flags)
@@ -91,6 +92,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-quake")) p.rsqrt_mode = NB_RSQRT_QUAKE;
         else if (!strcmp(argv[i], "-sequential")) p.sum_order = NB_SUM_SEQUENTIAL;
         else if (!strcmp(argv[i], "-kdk")) p.integrator = NB_INTEGRATOR_KDK;
+        else if (!strcmp(argv[i], "-collide")) p.extras |= NB_EXTRA_COLLIDE;
         else if (!strcmp(argv[i], "-dump") && i + 1 < argc) dump = argv[++i];
         else if (!strcmp(argv[i], "-load") && i + 1 < argc) {
             /* the header's parameters become the defaults of this run; later options override them */

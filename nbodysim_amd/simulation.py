@@ -67,13 +67,15 @@ class Simulation:
         sym_tile: int = 0,
         pos_rows: int = 0,
         static_items: bool = False,
+        collide: bool = False,
         library=None,
     ):
         """The last arguments (from ``uniform_mass`` on) are ``nb_params.flags`` and the launch-geometry tuning fields
         (0 / True = the library's automatic choice); the library reads no environment variables.  ``mass_scaling``: False / None
         (default) = both per-pair mass multiplies, True = fold the masses into the pair geometry wherever representable
         (include/nbody.h, NB_FLAG_MASS_SCALING), "measured" = the library measures at upload whether folding is harmless for
-        these bodies and folds only then (NB_FLAG_MASS_SCALING_MEASURED).  ``library``: another
+        these bodies and folds only then (NB_FLAG_MASS_SCALING_MEASURED).  ``collide``: end every step with the reference's
+        hard-sphere collisions (adds NB_EXTRA_COLLIDE to ``extras``; unsharded 2-D kick-drift only).  ``library``: another
         build of the library bound with ``_lib.bind`` (the tests' -DNB_TEST_HOOKS build); default the product."""
         lib = library if library is not None else L.load()
         if bodies.dtype not in (L.BODY_DTYPE, L.BODY3_DTYPE):
@@ -89,7 +91,7 @@ class Simulation:
         p.rsqrt_mode = {"exact": L.NB_RSQRT_EXACT, "quake": L.NB_RSQRT_QUAKE}[rsqrt]
         p.sum_order = {"tiled": L.NB_SUM_TILED, "sequential": L.NB_SUM_SEQUENTIAL}[order]
         p.integrator = {"kick_drift": L.NB_INTEGRATOR_KICK_DRIFT, "kdk": L.NB_INTEGRATOR_KDK}[integrator]
-        p.extras = extras
+        p.extras = extras | (L.NB_EXTRA_COLLIDE if collide else 0)
         p.device = device
         p.j_slices = j_slices
         p.i_begin = i_begin
@@ -186,6 +188,20 @@ class Simulation:
         L.check("nb_momentum", self._lib.nb_momentum(self._h, p, C.byref(lz)), self._lib)
         return (p[0], p[1], p[2]), lz.value
 
+    def collision_stats(self) -> dict:
+        """Counters of the collision path (``nb_collision_stats``; synchronises): pairs of the last step, pairs resolved since
+        creation, resolution rounds of the last step, steps that were over the pair capacity.  All 0 without ``collide``."""
+        last, total, ovf = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rounds = C.c_uint32()
+        L.check("nb_collision_stats", self._lib.nb_collision_stats(self._h, C.byref(last), C.byref(total), C.byref(rounds), C.byref(ovf)),
+                self._lib)
+        return {"pairs_last_step": int(last.value), "pairs_total": int(total.value), "rounds_last_step": int(rounds.value),
+                "overflow_steps": int(ovf.value)}
+
+    def collide_capacity(self, max_pairs: int) -> None:
+        """Set the pair capacity of the collision path (``nb_collide_capacity``)."""
+        L.check("nb_collide_capacity", self._lib.nb_collide_capacity(self._h, max_pairs), self._lib)
+
     def dump(self, path: str) -> None:
         L.check("nb_dump", self._lib.nb_dump(self._h, str(path).encode()), self._lib)
 
@@ -229,7 +245,7 @@ class Simulation:
         return info.as_dict()
 
     def describe(self) -> str:
-        buf = C.create_string_buffer(1024)
+        buf = C.create_string_buffer(2048)
         L.check("nb_describe", self._lib.nb_describe(self._h, buf, len(buf)), self._lib)
         return buf.value.decode()
 
