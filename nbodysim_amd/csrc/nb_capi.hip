@@ -56,8 +56,6 @@ extern "C" int nb_device_count(void)
 // j_begin/j_end are virtual indices that skip [gap_begin, gap_begin + gap_len)
 struct ForceJob { uint32_t j_begin, j_end, js, slab0; int P; uint32_t i_tiles; uint32_t gap_begin, gap_len; };
 
-constexpr int F32_WS = 4;   // waves of a workgroup sharing one i-set in force_tiled_f32 (in-workgroup j-split)
-
 // How a handle computes a step: chosen once by nb_create (step_path_of) and never changed.
 enum class StepPath {
     SYM,              // the whole system on this handle, symmetric kernel (force_sym_*)
@@ -245,7 +243,7 @@ static ForceJob plan_job(const nb_sim *s, uint32_t jb, uint32_t je, uint32_t sla
     // fp32: the 4 waves of a workgroup share 64 i-lanes and split each j-tile (WS = 4), a lane owns 2P
     // particles -> 128P particles per workgroup; fp64: 256 i-lanes, P particles per lane.
     const uint32_t lanes_i = s->fp64 ? 1u : 2u;                 // particles per lane per P
-    const uint32_t ilanes = s->fp64 ? (uint32_t)BLOCK : (uint32_t)BLOCK / F32_WS;
+    const uint32_t ilanes = s->fp64 ? (uint32_t)BLOCK : (uint32_t)BLOCK / TILED_F32_WS;
     const uint32_t target = 32u * (uint32_t)s->cus;             // workgroups wanted in the grid (profiles/history/r01_force_tiled_geometry_sweep.log)
     const uint32_t max_slices = 128;                            // bounds the slab traffic of `integrate`
     const uint32_t tiles = (jn + TJ - 1) / TJ;
@@ -1274,36 +1272,26 @@ static int launch_force(nb_sim *s, const ForceJob &j)
     const bool um = s->uniform_mass && !guard, scaled = s->mass_scaled && !guard;
     const uint32_t ib = (uint32_t)s->i_begin, ic = (uint32_t)s->i_count, grid = grid_blocks(j.i_tiles, j.js);
     with_layout(s, [&](auto L) {
-        using real = typename decltype(L)::real;
-        using vec = typename decltype(L)::vec;
+        using Lt = decltype(L);
+        using real = typename Lt::real;
+        using vec = typename Lt::vec;
         const real eps2 = (real)s->p.eps * (real)s->p.eps;   // Quadtree.hpp:19  e_sq(epsilon * epsilon)
         const vec *pos = (const vec *)s->pos[s->cur];
         vec *out = (vec *)s->partial + (size_t)j.slab0 * s->i_count;
         if constexpr (std::is_same_v<real, double>) {
             with_lanes<2>(j.P, [&](auto P) { with_flags([&](auto g) {
-                if constexpr (L.dims3)
-                    force_tiled3_f64<P, g, 4><<<grid, BLOCK, 0, s->stream>>>(pos, out, ib, ic, j.j_begin, j.j_end, j.js, j.i_tiles, eps2,
-                                                                             j.gap_begin, j.gap_len);
-                else
-                    force_tiled_f64<P, g, 4><<<grid, BLOCK, 0, s->stream>>>(pos, (const double *)s->mass, out, ib, ic, j.j_begin, j.j_end,
-                                                                            j.js, j.i_tiles, eps2, j.gap_begin, j.gap_len);
+                force_tiled_f64<Lt, P, g><<<grid, BLOCK, 0, s->stream>>>(pos, (const double *)s->mass, out, ib, ic, j.j_begin, j.j_end,
+                                                                         j.js, j.i_tiles, eps2, j.gap_begin, j.gap_len);
             }, guard); });
-        } else if constexpr (L.dims3) {
-            with_lanes<4>(j.P, [&](auto P) { with_flags([&](auto q, auto g) {
-                constexpr int RQ = q ? RSQ_QUAKE : RSQ_EXACT;
-                auto go = [&](auto kernel, float umv) {
-                    kernel<<<grid, BLOCK, 0, s->stream>>>(pos, out, ib, ic, j.j_begin, j.j_end, j.js, j.i_tiles, eps2, umv, j.gap_begin, j.gap_len);
-                };
-                if constexpr (!g)
-                    if (um) return go(force_tiled3_f32<P, RQ, false, 8, true>, s->um_mass);
-                go(force_tiled3_f32<P, RQ, g, 8, false>, 1.0f);
-            }, quake, guard); });
-        } else if (s->p.sum_order == NB_SUM_SEQUENTIAL) {
-            with_flags([&](auto q) {
-                force_seq_f32<q ? RSQ_QUAKE : RSQ_EXACT><<<(ic + BLOCK - 1) / BLOCK, BLOCK, 0, s->stream>>>(
-                    pos, (const float *)s->mass, out, ib, ic, j.j_begin, j.j_end, eps2);
-            }, quake);
         } else {
+            if constexpr (!L.dims3)      // nb_create refuses 3-D with the sequential order
+                if (s->p.sum_order == NB_SUM_SEQUENTIAL) {
+                    with_flags([&](auto q) {
+                        force_seq_f32<q ? RSQ_QUAKE : RSQ_EXACT><<<(ic + BLOCK - 1) / BLOCK, BLOCK, 0, s->stream>>>(
+                            pos, (const float *)s->mass, out, ib, ic, j.j_begin, j.j_end, eps2);
+                    }, quake);
+                    return;
+                }
             with_lanes<4>(j.P, [&](auto P) { with_flags([&](auto q, auto g) {
                 constexpr int RQ = q ? RSQ_QUAKE : RSQ_EXACT;
                 auto go = [&](auto kernel, float umv) {
@@ -1311,11 +1299,11 @@ static int launch_force(nb_sim *s, const ForceJob &j)
                                                           j.i_tiles, eps2, umv, j.gap_begin, j.gap_len);
                 };
                 if constexpr (!g) {
-                    if (um) return go(force_tiled_f32<P, RQ, false, 8, true, F32_WS>, s->um_mass);
-                    if constexpr (RQ == RSQ_EXACT)     // individual masses folded into the pair geometry: no mass multiply in the body
-                        if (scaled) return go(force_tiled_f32<P, RSQ_EXACT, false, 8, false, F32_WS, true>, 1.0f);
+                    if (um) return go(force_tiled_f32<Lt, P, RQ, false, true>, s->um_mass);
+                    if constexpr (RQ == RSQ_EXACT && !L.dims3)     // individual masses folded into the pair geometry: no mass multiply in the body
+                        if (scaled) return go(force_tiled_f32<Lt, P, RSQ_EXACT, false, false, true>, 1.0f);
                 }
-                go(force_tiled_f32<P, RQ, g, 8, false, F32_WS>, 1.0f);
+                go(force_tiled_f32<Lt, P, RQ, g, false>, 1.0f);
             }, quake, guard); });
         }
     });
@@ -2058,7 +2046,7 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
              "two-phase P/slices local=%d/%u remote=%d/%u | uniform_mass=%d mass_scaled=%d mass_scaling_check=%.1e | symmetric=%d tile=%u chunk_pairs=%d items=%u chunks/item=%u late=%u slabs=%.1f+%.1f MiB | CUs=%d",
              s->n, s->i_begin, s->i_count, s->fp64 ? "fp64" : "fp32", s->dims3 ? " 3-D" : "",
              s->p.rsqrt_mode == NB_RSQRT_QUAKE ? "quake" : "exact", seq ? "sequential" : "tiled",
-             BLOCK, (seq || s->fp64) ? 1 : F32_WS, seq ? 1 : (s->fp64 ? a.P : 2 * a.P), a.i_tiles, a.js,
+             BLOCK, (seq || s->fp64) ? 1 : TILED_F32_WS, seq ? 1 : (s->fp64 ? a.P : 2 * a.P), a.i_tiles, a.js,
              seq ? a.i_tiles : grid_blocks(a.i_tiles, a.js), TJ,
              s->job_local.P, s->job_local.js, s->job_remote.P, s->job_remote.js, (int)s->uniform_mass, (int)s->mass_scaled, (double)s->mass_scaling_dev,
              (int)symmetric(s), s->sym_sb, (int)sym_uses_pairs(s), s->sym_items, s->sym_L, s->sym_items_late,

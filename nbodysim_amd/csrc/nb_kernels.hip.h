@@ -11,15 +11,16 @@
 //   force_sym_f32 / force_sym_f64   symmetric fast path: every unordered pair once (Newton's third
 //                                   law); stationary particles in registers, 64-particle travelling
 //                                   chunks rotated through the lanes with ds_bpermute_b32
-//   force_tiled_f32 / force_tiled_f64   one-sided: j-particles through a double-buffered LDS tile,
+//   force_tiled_f32 / force_tiled_f64   one-sided (2-D and 3-D): j-particles through a double-buffered LDS tile,
 //                                   one broadcast ds_read_b128 per j, 2P packed i-particles per lane,
 //                                   grid- and workgroup-level j-split
 //   force_seq_f32                   the reference's summation order, bit-exact parity mode
 //   sym_gather / integrate          fixed-order sums of the partial slabs + kick/drift (no atomics:
 //                                   results are reproducible run to run)
 //   pack/unpack/energy/sum_partials AoS <-> SoA, diagnostics, in-process reduce-scatter
-// integrate, kick/drift, pack/unpack, energy and momentum are keyed on a Layout (precision x 2-D / 3-D) and
-// serve the 3-D handles too; the 3-D force kernels and their gather are in nb_kernels3d.hip.h.
+// The one-sided force kernels, integrate, kick/drift, pack/unpack, energy and momentum are keyed on a Layout
+// (precision x 2-D / 3-D) and serve the 3-D handles too; the 3-D symmetric kernels and their gather are in
+// nb_kernels3d.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -317,41 +318,42 @@ void quake_rsqrt_array(const float *__restrict__ x, float *__restrict__ y_scalar
 
 
 // ---------------------------------------------------------------------------
-// force_tiled_f32 — the fast path.
-//   pos      (x,y) interleaved, full-n replica of the positions at t_n
-//   mass     full n
+// force_tiled_f32 — the one-sided fast path, 2-D and 3-D (L = Layout<float, D3>).
+//   pos      positions, full-n replica at t_n: float2 (x,y) in 2-D, float4 {x,y,z,m} in 3-D
+//   mass     full n (2-D; 3-D takes the mass from pos.w)
+//   sigma    m^(-1/2), full n (MS only)
 //   partial  [js][i_count] partial accelerations of this launch's slabs
 //   i_begin/i_count   the owned block (particles this GPU integrates)
 //   j_begin/j_end     the j range of this launch, cut into js slices; the range is in
 //                     VIRTUAL indices that skip [gap_begin, gap_begin+gap_len): a sharded
 //                     rank sweeps "everything but my own block" in one launch
-// WS = how many of the workgroup's 4 waves share one set of i-particles and split each
-// j-tile between them (in-workgroup j-split):
-//   WS = 1  every wave owns its own i's (256 i-lanes), each wave walks the whole tile;
-//   WS = 4  the 4 waves own the SAME 64 i-lanes and walk one quarter of the tile each;
-//           their partial sums are combined through LDS in wave order at the end
-//           (deterministic), so the workgroup still writes ONE slab row per particle.
-//           Four times the workgroups for the same number of slabs: this is what keeps
-//           256 CUs busy when i-particles are scarce (small N, sharded ranks) without
-//           multiplying the slab traffic.
+// The TILED_F32_WS = 4 waves of a workgroup own the SAME 64 i-lanes and walk one quarter of each
+// j-tile (in-workgroup j-split); their partial sums are combined through LDS in wave order at the
+// end (deterministic), so the workgroup still writes ONE slab row per particle.  Four times the
+// workgroups for the same number of slabs: this is what keeps 256 CUs busy when i-particles are
+// scarce (small N, sharded ranks) without multiplying the slab traffic.
 // Lane l (of i-lane group) of tile T owns particles
-//   i_begin + T*IT + p*(2*LANES_I) + 2l + {0,1},  p < P,  IT = LANES_I*2P,  LANES_I = 256/WS.
+//   i_begin + T*IT + p*(2*LANES_I) + 2l + {0,1},  p < P,  IT = LANES_I*2P,  LANES_I = 64.
 // ---------------------------------------------------------------------------
-template <int P, int RSQ, bool GUARD, int UNROLL, bool UM = false, int WS = 1, bool MS = false>
+constexpr int TILED_F32_WS = 4;   // waves of a workgroup sharing one i-set (the host plans with BLOCK / TILED_F32_WS i-lanes)
+
+template <typename L, int P, int RSQ, bool GUARD, bool UM, bool MS>
 __device__ __forceinline__
-void force_tiled_f32_body(const float2 *__restrict__ pos, const float *__restrict__ mass, const float *__restrict__ sigma,
-                          float2 *__restrict__ partial,
+void force_tiled_f32_body(const typename L::vec *__restrict__ pos, const float *__restrict__ mass, const float *__restrict__ sigma,
+                          typename L::vec *__restrict__ partial,
                           uint32_t i_begin, uint32_t i_count,
                           uint32_t j_begin, uint32_t j_end,
-                          uint32_t js, uint32_t i_tiles, float eps2, float um_mass = 1.0f,
-                          uint32_t gap_begin = 0xffffffffu, uint32_t gap_len = 0)
+                          uint32_t js, uint32_t i_tiles, float eps2, float um_mass,
+                          uint32_t gap_begin, uint32_t gap_len)
 {
-    static_assert(WS == 1 || WS == 2 || WS == 4, "WS waves share an i-set");
     static_assert(!(MS && (UM || GUARD)), "mass scaling is for individual masses with eps > 0");
+    static_assert(!(MS && L::dims3), "mass scaling is 2-D only");
+    constexpr int WS = TILED_F32_WS, UNROLL = 8;
     constexpr uint32_t LANES_I = BLOCK / WS;          // distinct i-lanes in the workgroup
     constexpr uint32_t IT = LANES_I * 2 * P;          // particles per workgroup
     constexpr uint32_t JW = TJ / WS;                  // j's of a tile walked by one wave group
-    constexpr uint32_t RED = (WS - 1) * P * LANES_I;  // v4f slots of the final cross-wave reduction
+    constexpr uint32_t SL = L::dims3 ? 2 : 1;         // v4f slots per (p, lane) in the reduction: 4 sums in 2-D, 6 in 8 slots in 3-D
+    constexpr uint32_t RED = (WS - 1) * P * LANES_I * SL;
     constexpr uint32_t SMEM = 2 * TJ > RED ? 2 * TJ : RED;
     __shared__ v4f smem[SMEM];
     v4f (*tile)[TJ] = reinterpret_cast<v4f (*)[TJ]>(smem);
@@ -360,7 +362,7 @@ void force_tiled_f32_body(const float2 *__restrict__ pos, const float *__restric
     if (!tm.valid) return;
     const uint32_t t = threadIdx.x;
     const uint32_t lane_i = t % LANES_I;              // which i-lane
-    const uint32_t w = t / LANES_I;                   // which share of every tile (0 when WS == 1)
+    const uint32_t w = t / LANES_I;                   // which share of every tile
 
     // slice bounds, multiples of TJ from j_begin
     const uint32_t jn = j_end - j_begin;
@@ -368,30 +370,36 @@ void force_tiled_f32_body(const float2 *__restrict__ pos, const float *__restric
     const uint32_t s0 = j_begin + min(tm.slice * slice_len, jn);
     const uint32_t s1 = j_begin + min((tm.slice + 1) * slice_len, jn);
 
-    // i-particles of this lane
-    v2f xi[P], yi[P], ax[P], ay[P];
+    // i-particles of this lane (zi, az: 3-D only)
+    v2f xi[P], yi[P], zi[P], ax[P], ay[P], az[P];
     uint32_t li[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         li[p] = tm.i_tile * IT + (uint32_t)p * (LANES_I * 2) + 2u * lane_i;
         const uint32_t l0 = min(li[p], i_count - 1), l1 = min(li[p] + 1, i_count - 1);
-        const float2 p0 = pos[i_begin + l0], p1 = pos[i_begin + l1];
+        const auto p0 = pos[i_begin + l0], p1 = pos[i_begin + l1];
         xi[p] = (v2f){p0.x, p1.x};
         yi[p] = (v2f){p0.y, p1.y};
         ax[p] = (v2f){0.f, 0.f};
         ay[p] = (v2f){0.f, 0.f};
+        if constexpr (L::dims3) { zi[p] = (v2f){p0.z, p1.z}; az[p] = (v2f){0.f, 0.f}; }
     }
     const v2f e2 = {eps2, eps2};
 
     const uint32_t ntiles = (s1 - s0 + TJ - 1) / TJ;
-    // One j-particle as the LDS tile holds it: {x, y, m, m}; mass-scaled (MS, see MM_SCALED at force_sym_f32): the
-    // pre-multiplied position and the scaled softening {sigma x, sigma y, -sigma, sigma^2 eps^2}, sigma = m^(-1/2) —
-    // the body then needs no mass multiply at all (8 + 2 instructions per two pairs, like the equal-mass form).
+    // One j-particle as the LDS tile holds it: {x, y, m, m} in 2-D, the position record {x, y, z, m} in 3-D; mass-scaled
+    // (MS, see MM_SCALED at force_sym_f32): the pre-multiplied position and the scaled softening {sigma x, sigma y, -sigma,
+    // sigma^2 eps^2}, sigma = m^(-1/2) — the body then needs no mass multiply at all (8 + 2 instructions per two pairs, like
+    // the equal-mass form).
     auto stage = [&](uint32_t j) -> v4f {
-        if (j >= s1) return MS ? (v4f){PAD_XY, PAD_XY, -1.0f, eps2} : (v4f){PAD_XY, PAD_XY, 0.f, 0.f};
+        if (j >= s1) {
+            if constexpr (L::dims3) return (v4f){PAD_XY, PAD_XY, PAD_XY, 0.f};
+            else return MS ? (v4f){PAD_XY, PAD_XY, -1.0f, eps2} : (v4f){PAD_XY, PAD_XY, 0.f, 0.f};
+        }
         const uint32_t jg = j + (j >= gap_begin ? gap_len : 0u);
-        const float2 pj = pos[jg];
-        if constexpr (MS) { const float sg = sigma[jg]; return (v4f){pj.x * sg, pj.y * sg, -sg, (sg * sg) * eps2}; }
+        const auto pj = pos[jg];
+        if constexpr (L::dims3) return (v4f){pj.x, pj.y, pj.z, pj.w};
+        else if constexpr (MS) { const float sg = sigma[jg]; return (v4f){pj.x * sg, pj.y * sg, -sg, (sg * sg) * eps2}; }
         else { const float mj = mass[jg]; return (v4f){pj.x, pj.y, mj, mj}; }
     };
     tile[0][t] = stage(s0 + t);
@@ -405,10 +413,11 @@ void force_tiled_f32_body(const float2 *__restrict__ pos, const float *__restric
 #pragma unroll UNROLL
         for (int jj = 0; jj < (int)JW; ++jj) {
             const v4f q = cur[jj];                 // broadcast ds_read_b128
-            const v2f xj = {q.x, q.x}, yj = {q.y, q.y}, mj = {q.z, q.w};
+            const v2f xj = {q.x, q.x}, yj = {q.y, q.y}, zj = {q.z, q.z};
+            const v2f mj = L::dims3 ? (v2f){q.w, q.w} : (v2f){q.z, q.w};
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                v2f dx, dy, r2, inv;
+                v2f dx, dy, dz, r2, inv;
                 if constexpr (MS) {
                     const v2f ns = {q.z, q.z};
                     dx = __builtin_elementwise_fma(ns, xi[p], xj);     // sigma_j (x_j - x_i)
@@ -416,6 +425,7 @@ void force_tiled_f32_body(const float2 *__restrict__ pos, const float *__restric
                 } else {
                     dx = xj - xi[p];               // v_pk_add_f32 (neg)
                     dy = yj - yi[p];
+                    if constexpr (L::dims3) dz = zj - zi[p];
                 }
                 if constexpr (MS) {
                     r2 = __builtin_elementwise_fma(dx, dx, (v2f){q.w, q.w});
@@ -425,6 +435,7 @@ void force_tiled_f32_body(const float2 *__restrict__ pos, const float *__restric
                     // eps == 0 or too small for 1/r^3 of a coincident pair to stay finite: keep the reference's
                     // `if (r_sq > 0)` around `fast_inv_sqrt(r_sq + e_sq)` (Quadtree.hpp:139-140)
                     r2 = __builtin_elementwise_fma(dy, dy, dx * dx);
+                    if constexpr (L::dims3) r2 = __builtin_elementwise_fma(dz, dz, r2);
                     const v2f t2 = r2 + e2;
                     if constexpr (RSQ == RSQ_EXACT)
                         inv = (v2f){__builtin_amdgcn_rsqf(t2.x), __builtin_amdgcn_rsqf(t2.y)};
@@ -435,6 +446,7 @@ void force_tiled_f32_body(const float2 *__restrict__ pos, const float *__restric
                 } else {
                     r2 = __builtin_elementwise_fma(dx, dx, e2);
                     r2 = __builtin_elementwise_fma(dy, dy, r2);
+                    if constexpr (L::dims3) r2 = __builtin_elementwise_fma(dz, dz, r2);
                     if constexpr (RSQ == RSQ_EXACT)
                         inv = (v2f){__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
                     else
@@ -446,56 +458,76 @@ void force_tiled_f32_body(const float2 *__restrict__ pos, const float *__restric
                 else s = (mj * inv) * inv2;                 // m / r^3
                 ax[p] = __builtin_elementwise_fma(s, dx, ax[p]);
                 ay[p] = __builtin_elementwise_fma(s, dy, ay[p]);
+                if constexpr (L::dims3) az[p] = __builtin_elementwise_fma(s, dz, az[p]);
             }
         }
         if (it + 1 < ntiles) tile[(it + 1) & 1][t] = nxt;
         __syncthreads();
     }
 
-    if constexpr (WS > 1) {
-        // combine the WS partial sums of each particle in wave-group order 0,1,..,WS-1
-        // (the tile buffers are free: the loop ended on a barrier)
-        if (w > 0) {
-#pragma unroll
-            for (int p = 0; p < P; ++p)
-                smem[((w - 1) * P + p) * LANES_I + lane_i] = (v4f){ax[p].x, ay[p].x, ax[p].y, ay[p].y};
-        }
-        __syncthreads();
-        if (w > 0) return;
+    // combine the WS partial sums of each particle in wave-group order 0,1,..,WS-1
+    // (the tile buffers are free: the loop ended on a barrier)
+    if (w > 0) {
 #pragma unroll
         for (int p = 0; p < P; ++p) {
+            v4f *r = &smem[(((w - 1) * P + p) * LANES_I + lane_i) * SL];
+            if constexpr (L::dims3) {
+                r[0] = (v4f){ax[p].x, ay[p].x, az[p].x, 0.f};
+                r[1] = (v4f){ax[p].y, ay[p].y, az[p].y, 0.f};
+            } else r[0] = (v4f){ax[p].x, ay[p].x, ax[p].y, ay[p].y};
+        }
+    }
+    __syncthreads();
+    if (w > 0) return;
 #pragma unroll
-            for (int k = 0; k < WS - 1; ++k) {
-                const v4f r = smem[(k * P + p) * LANES_I + lane_i];
-                ax[p] += (v2f){r.x, r.z};
-                ay[p] += (v2f){r.y, r.w};
+    for (int p = 0; p < P; ++p) {
+#pragma unroll
+        for (int k = 0; k < WS - 1; ++k) {
+            const v4f *r = &smem[((k * P + p) * LANES_I + lane_i) * SL];
+            if constexpr (L::dims3) {
+                ax[p] += (v2f){r[0].x, r[1].x};
+                ay[p] += (v2f){r[0].y, r[1].y};
+                az[p] += (v2f){r[0].z, r[1].z};
+            } else {
+                ax[p] += (v2f){r[0].x, r[0].z};
+                ay[p] += (v2f){r[0].y, r[0].w};
             }
+        }
+        if constexpr (L::dims3) {       // stored at once: after the whole reduction, as in 2-D, costs 28 VGPRs at P = 4
+            float4 *__restrict__ out = partial + (size_t)tm.slice * i_count;
+            if constexpr (UM) { ax[p] *= um_mass; ay[p] *= um_mass; az[p] *= um_mass; }
+            if (li[p] < i_count) out[li[p]] = make_float4(ax[p].x, ay[p].x, az[p].x, 0.f);
+            if (li[p] + 1 < i_count) out[li[p] + 1] = make_float4(ax[p].y, ay[p].y, az[p].y, 0.f);
         }
     }
 
-    float2 *__restrict__ out = partial + (size_t)tm.slice * i_count;
+    if constexpr (!L::dims3) {
+        float2 *__restrict__ out = partial + (size_t)tm.slice * i_count;
 #pragma unroll
-    for (int p = 0; p < P; ++p) {
-        if constexpr (UM) { ax[p] *= um_mass; ay[p] *= um_mass; }
-        if (li[p] + 1 < i_count) {
-            *reinterpret_cast<float4 *>(&out[li[p]]) = make_float4(ax[p].x, ay[p].x, ax[p].y, ay[p].y);
-        } else if (li[p] < i_count) {
-            out[li[p]] = make_float2(ax[p].x, ay[p].x);
+        for (int p = 0; p < P; ++p) {
+            if constexpr (UM) { ax[p] *= um_mass; ay[p] *= um_mass; }
+            if (li[p] + 1 < i_count) {
+                *reinterpret_cast<float4 *>(&out[li[p]]) = make_float4(ax[p].x, ay[p].x, ax[p].y, ay[p].y);
+            } else if (li[p] < i_count) {
+                out[li[p]] = make_float2(ax[p].x, ay[p].x);
+            }
         }
     }
 }
 
-template <int P, int RSQ, bool GUARD, int UNROLL, bool UM = false, int WS = 1, bool MS = false>
+// The body stays a separate inlined function: the compiler simplifies it on its own before inlining it, and folding it
+// into the kernel changes the 2-D instruction schedule and register assignment (not the arithmetic).
+template <typename L, int P, int RSQ, bool GUARD, bool UM = false, bool MS = false>
 __global__ __launch_bounds__(BLOCK)
-void force_tiled_f32(const float2 *__restrict__ pos, const float *__restrict__ mass, const float *__restrict__ sigma,
-                     float2 *__restrict__ partial,
+void force_tiled_f32(const typename L::vec *__restrict__ pos, const float *__restrict__ mass, const float *__restrict__ sigma,
+                     typename L::vec *__restrict__ partial,
                      uint32_t i_begin, uint32_t i_count,
                      uint32_t j_begin, uint32_t j_end,
                      uint32_t js, uint32_t i_tiles, float eps2, float um_mass,
                      uint32_t gap_begin, uint32_t gap_len)
 {
-    force_tiled_f32_body<P, RSQ, GUARD, UNROLL, UM, WS, MS>(pos, mass, sigma, partial, i_begin, i_count, j_begin, j_end, js, i_tiles, eps2,
-                                                            um_mass, gap_begin, gap_len);
+    force_tiled_f32_body<L, P, RSQ, GUARD, UM, MS>(pos, mass, sigma, partial, i_begin, i_count, j_begin, j_end, js, i_tiles, eps2,
+                                                   um_mass, gap_begin, gap_len);
 }
 
 // ---------------------------------------------------------------------------
@@ -1259,9 +1291,9 @@ void force_seq_f32(const float2 *__restrict__ pos, const float *__restrict__ mas
 }
 
 // ---------------------------------------------------------------------------
-// force_tiled_f64 — fp64 extension (BASELINE config 5).  One i per lane per
-// register slot (P slots), same tiling; 1/sqrt from v_rsq_f64 refined by one
-// third-order step (relative error ~1e-16 after refinement).
+// force_tiled_f64 — fp64 extension (BASELINE config 5), 2-D and 3-D (L = Layout<double, D3>).
+// One i per lane per register slot (P slots), same tiling; 1/sqrt from v_rsq_f64 refined by
+// one third-order step (relative error ~1e-16 after refinement).
 // ---------------------------------------------------------------------------
 // A floating-point constant held in a VGPR pair for the whole kernel.  gfx950 (GFX9 encoding) cannot put a 64-bit
 // literal into a VOP3 v_fma_f64, so `fma(e, 1.875, 1.5)` would otherwise be compiled as v_mov_b32 x2 (re-materialising
@@ -1296,18 +1328,22 @@ __device__ __forceinline__ double rsqrt3_f64(double x, double k15, double k1875)
     return __builtin_fma(y3 * e, c, y3);
 }
 
-template <int P, bool GUARD, int UNROLL>
+// one j-particle as the LDS tile of force_tiled_f64 holds it: {x, y, m, 0} in 2-D, the position record {x, y, z, m} in 3-D
+__device__ __forceinline__ double4 tile_record(double2 p, double m) { return make_double4(p.x, p.y, m, 0.0); }
+__device__ __forceinline__ double4 tile_record(double4 p, double) { return p; }
+
+template <typename L, int P, bool GUARD>
 __global__ __launch_bounds__(BLOCK)
-void force_tiled_f64(const double2 *__restrict__ pos, const double *__restrict__ mass,
-                     double2 *__restrict__ partial,
+void force_tiled_f64(const typename L::vec *__restrict__ pos, const double *__restrict__ mass,
+                     typename L::vec *__restrict__ partial,
                      uint32_t i_begin, uint32_t i_count,
                      uint32_t j_begin, uint32_t j_end,
                      uint32_t js, uint32_t i_tiles, double eps2,
                      uint32_t gap_begin, uint32_t gap_len)
 {
+    constexpr int UNROLL = 4;
     constexpr uint32_t IT = BLOCK * P;
-    struct alignas(16) JD { double x, y, m, pad; };
-    __shared__ JD tile[2][TJ];
+    __shared__ double4 tile[2][TJ];
     const double k15 = vgpr_const(1.5), k1875 = vgpr_const(1.875);
 
     const TileMap tm = decode_block(blockIdx.x, i_tiles, js);
@@ -1318,53 +1354,66 @@ void force_tiled_f64(const double2 *__restrict__ pos, const double *__restrict__
     const uint32_t s0 = j_begin + min(tm.slice * slice_len, jn);
     const uint32_t s1 = j_begin + min((tm.slice + 1) * slice_len, jn);
 
-    double xi[P], yi[P], ax[P], ay[P];
+    double xi[P], yi[P], zi[P], ax[P], ay[P], az[P];     // zi, az: 3-D only
     uint32_t li[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         li[p] = tm.i_tile * IT + (uint32_t)p * BLOCK + t;
-        const double2 p0 = pos[i_begin + min(li[p], i_count - 1)];
+        const auto p0 = pos[i_begin + min(li[p], i_count - 1)];
         xi[p] = p0.x; yi[p] = p0.y; ax[p] = 0.0; ay[p] = 0.0;
+        if constexpr (L::dims3) { zi[p] = p0.z; az[p] = 0.0; }
     }
     const uint32_t ntiles = (s1 - s0 + TJ - 1) / TJ;
+    // past s1: mass 0 contributes nothing (eps > 0 or guarded).  pj is assigned under `if`: a select between pos[jg] and a
+    // zero record would be made in scratch memory.
     {
         const uint32_t j = s0 + t;
-        double2 pj = make_double2(0.0, 0.0); double mj = 0.0;
-        if (j < s1) { const uint32_t jg = j + (j >= gap_begin ? gap_len : 0u); pj = pos[jg]; mj = mass[jg]; }
-        tile[0][t] = JD{pj.x, pj.y, mj, 0.0};
+        typename L::vec pj; double mj = 0.0;
+        pj.x = pj.y = 0.0; if constexpr (L::dims3) pj.z = pj.w = 0.0;
+        if (j < s1) { const uint32_t jg = j + (j >= gap_begin ? gap_len : 0u); pj = pos[jg]; mj = mass_at<L>(pos, mass, jg); }
+        tile[0][t] = tile_record(pj, mj);
     }
     __syncthreads();
     for (uint32_t it = 0; it < ntiles; ++it) {
-        double2 pn = make_double2(0.0, 0.0); double mn = 0.0;
+        typename L::vec pn; double mn = 0.0;
+        pn.x = pn.y = 0.0; if constexpr (L::dims3) pn.z = pn.w = 0.0;
         const uint32_t jn1 = s0 + (it + 1) * TJ + t;
-        if (jn1 < s1) { const uint32_t jg = jn1 + (jn1 >= gap_begin ? gap_len : 0u); pn = pos[jg]; mn = mass[jg]; }
-        const JD *__restrict__ cur = tile[it & 1];
+        if (jn1 < s1) { const uint32_t jg = jn1 + (jn1 >= gap_begin ? gap_len : 0u); pn = pos[jg]; mn = mass_at<L>(pos, mass, jg); }
+        const double4 *__restrict__ cur = tile[it & 1];
 #pragma unroll UNROLL
         for (int jj = 0; jj < TJ; ++jj) {
-            const double xj = cur[jj].x, yj = cur[jj].y, mj = cur[jj].m;
+            const double4 q = cur[jj];
+            const double mj = L::dims3 ? q.w : q.z;
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                const double dx = xj - xi[p], dy = yj - yi[p];
-                double r2, inv3;
+                const double dx = q.x - xi[p], dy = q.y - yi[p];
+                double dz, r2, inv3;
+                if constexpr (L::dims3) dz = q.z - zi[p];
                 if constexpr (GUARD) {
                     r2 = __builtin_fma(dy, dy, dx * dx);
+                    if constexpr (L::dims3) r2 = __builtin_fma(dz, dz, r2);
                     inv3 = r2 > 0.0 ? rsqrt3_f64(r2, k15, k1875) : 0.0;
                 } else {
                     r2 = __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2));
+                    if constexpr (L::dims3) r2 = __builtin_fma(dz, dz, r2);
                     inv3 = rsqrt3_f64(r2, k15, k1875);
                 }
                 const double s = mj * inv3;
                 ax[p] = __builtin_fma(s, dx, ax[p]);
                 ay[p] = __builtin_fma(s, dy, ay[p]);
+                if constexpr (L::dims3) az[p] = __builtin_fma(s, dz, az[p]);
             }
         }
-        if (it + 1 < ntiles) tile[(it + 1) & 1][t] = JD{pn.x, pn.y, mn, 0.0};
+        if (it + 1 < ntiles) tile[(it + 1) & 1][t] = tile_record(pn, mn);
         __syncthreads();
     }
-    double2 *__restrict__ out = partial + (size_t)tm.slice * i_count;
+    typename L::vec *__restrict__ out = partial + (size_t)tm.slice * i_count;
 #pragma unroll
-    for (int p = 0; p < P; ++p)
-        if (li[p] < i_count) out[li[p]] = make_double2(ax[p], ay[p]);
+    for (int p = 0; p < P; ++p) {
+        if (li[p] >= i_count) continue;
+        if constexpr (L::dims3) out[li[p]] = make_double4(ax[p], ay[p], az[p], 0.0);
+        else out[li[p]] = make_double2(ax[p], ay[p]);
+    }
 }
 
 // a += b over the components (x, y [, z]); w, the 3-D mass slot, is left as it is

@@ -9,123 +9,15 @@
 //
 // Device layout: positions as real4 {x, y, z, m} (float4: one 16-byte load per particle; double4: two; the
 // mass rides along), velocities / accelerations / slab rows as real4 {·, ·, ·, 0}.
-// This file holds the 3-D force kernels and the gather of their slabs, in fp32 and fp64:
+// This file holds the 3-D symmetric force kernels and the gather of their slabs, in fp32 and fp64:
 //   force_sym3_f32 / _f64    symmetric (Newton's third law) fast path, lane-rotated travelling particles
-//   force_tiled3_f32 / _f64  one-sided LDS-tiled kernel (small n, eps = 0, all-gather sharding, cross-check);
-//                            the j range skips [gap_begin, gap_begin + gap_len) like the 2-D kernels
 //   sym_gather3              sum of the symmetric slabs, one particle per thread
-// integrate, kick / drift, pack / unpack, energy, momentum and sum_partials are shared with 2-D: the kernels of
-// nb_kernels.hip.h keyed on Layout<real, true>.
+// The one-sided force kernels (force_tiled_f32 / _f64), integrate, kick / drift, pack / unpack, energy, momentum and
+// sum_partials are shared with 2-D: the kernels of nb_kernels.hip.h keyed on Layout<real, true>.
 #pragma once
 #include "nb_kernels.hip.h"
 
 namespace nbk {
-
-// ---------------------------------------------------------------------------
-// force_tiled3_f32 — one-sided, LDS-tiled (the 3-D twin of force_tiled_f32, WS = 4).
-// Tile entries are the position records themselves: float4 {x, y, z, m}.
-// ---------------------------------------------------------------------------
-template <int P, int RSQ, bool GUARD, int UNROLL, bool UM>
-__global__ __launch_bounds__(BLOCK)
-void force_tiled3_f32(const float4 *__restrict__ pos, float4 *__restrict__ partial,
-                      uint32_t i_begin, uint32_t i_count, uint32_t j_begin, uint32_t j_end,
-                      uint32_t js, uint32_t i_tiles, float eps2, float um_mass, uint32_t gap_begin, uint32_t gap_len)
-{
-    constexpr int WS = 4;
-    constexpr uint32_t LANES_I = BLOCK / WS, IT = LANES_I * 2 * P, JW = TJ / WS;
-    constexpr uint32_t RED = (WS - 1) * P * LANES_I * 2;      // two float4 per (p, lane): 6 sums in 8 slots
-    constexpr uint32_t SMEM = 2 * TJ > RED ? 2 * TJ : RED;
-    __shared__ v4f smem[SMEM];
-    v4f (*tile)[TJ] = reinterpret_cast<v4f (*)[TJ]>(smem);
-
-    const TileMap tm = decode_block(blockIdx.x, i_tiles, js);
-    if (!tm.valid) return;
-    const uint32_t t = threadIdx.x, lane_i = t % LANES_I, w = t / LANES_I;
-    const uint32_t jn = j_end - j_begin;
-    const uint32_t slice_len = (((jn + js - 1) / js + TJ - 1) / TJ) * TJ;
-    const uint32_t s0 = j_begin + min(tm.slice * slice_len, jn);
-    const uint32_t s1 = j_begin + min((tm.slice + 1) * slice_len, jn);
-
-    v2f xi[P], yi[P], zi[P], ax[P], ay[P], az[P];
-    uint32_t li[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        li[p] = tm.i_tile * IT + (uint32_t)p * (LANES_I * 2) + 2u * lane_i;
-        const float4 p0 = pos[i_begin + min(li[p], i_count - 1)], p1 = pos[i_begin + min(li[p] + 1, i_count - 1)];
-        xi[p] = (v2f){p0.x, p1.x}; yi[p] = (v2f){p0.y, p1.y}; zi[p] = (v2f){p0.z, p1.z};
-        ax[p] = ay[p] = az[p] = (v2f){0.f, 0.f};
-    }
-    const v2f e2 = {eps2, eps2};
-    const uint32_t ntiles = (s1 - s0 + TJ - 1) / TJ;
-    const v4f pad = {PAD_XY, PAD_XY, PAD_XY, 0.f};
-    {
-        const uint32_t j = s0 + t;
-        v4f q = pad;
-        if (j < s1) { const float4 r = pos[j + (j >= gap_begin ? gap_len : 0u)]; q = (v4f){r.x, r.y, r.z, r.w}; }
-        tile[0][t] = q;
-    }
-    __syncthreads();
-    for (uint32_t it = 0; it < ntiles; ++it) {
-        v4f qn = pad;
-        const uint32_t jn1 = s0 + (it + 1) * TJ + t;
-        if (jn1 < s1) { const float4 r = pos[jn1 + (jn1 >= gap_begin ? gap_len : 0u)]; qn = (v4f){r.x, r.y, r.z, r.w}; }
-        const v4f *__restrict__ cur = tile[it & 1] + w * JW;
-#pragma unroll UNROLL
-        for (int jj = 0; jj < (int)JW; ++jj) {
-            const v4f q = cur[jj];
-            const v2f xj = {q.x, q.x}, yj = {q.y, q.y}, zj = {q.z, q.z}, mj = {q.w, q.w};
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                const v2f dx = xj - xi[p], dy = yj - yi[p], dz = zj - zi[p];
-                v2f r2, inv;
-                if constexpr (GUARD) {
-                    r2 = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
-                    const v2f t2 = r2 + e2;
-                    if constexpr (RSQ == RSQ_EXACT) inv = (v2f){__builtin_amdgcn_rsqf(t2.x), __builtin_amdgcn_rsqf(t2.y)};
-                    else inv = quake_rsqrt2(t2);
-                    inv.x = r2.x > 0.f ? inv.x : 0.f;
-                    inv.y = r2.y > 0.f ? inv.y : 0.f;
-                } else {
-                    r2 = __builtin_elementwise_fma(dx, dx, e2);
-                    r2 = __builtin_elementwise_fma(dy, dy, r2);
-                    r2 = __builtin_elementwise_fma(dz, dz, r2);
-                    if constexpr (RSQ == RSQ_EXACT) inv = (v2f){__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
-                    else inv = quake_rsqrt2(r2);
-                }
-                const v2f inv2 = inv * inv;
-                v2f s;
-                if constexpr (UM) s = inv * inv2; else s = (mj * inv) * inv2;
-                ax[p] = __builtin_elementwise_fma(s, dx, ax[p]);
-                ay[p] = __builtin_elementwise_fma(s, dy, ay[p]);
-                az[p] = __builtin_elementwise_fma(s, dz, az[p]);
-            }
-        }
-        if (it + 1 < ntiles) tile[(it + 1) & 1][t] = qn;
-        __syncthreads();
-    }
-    // combine the WS wave groups in order through LDS
-    if (w > 0) {
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            smem[(((w - 1) * P + p) * LANES_I + lane_i) * 2 + 0] = (v4f){ax[p].x, ay[p].x, az[p].x, 0.f};
-            smem[(((w - 1) * P + p) * LANES_I + lane_i) * 2 + 1] = (v4f){ax[p].y, ay[p].y, az[p].y, 0.f};
-        }
-    }
-    __syncthreads();
-    if (w > 0) return;
-    float4 *__restrict__ out = partial + (size_t)tm.slice * i_count;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-#pragma unroll
-        for (int k = 0; k < WS - 1; ++k) {
-            const v4f r0 = smem[((k * P + p) * LANES_I + lane_i) * 2 + 0], r1 = smem[((k * P + p) * LANES_I + lane_i) * 2 + 1];
-            ax[p] += (v2f){r0.x, r1.x}; ay[p] += (v2f){r0.y, r1.y}; az[p] += (v2f){r0.z, r1.z};
-        }
-        if constexpr (UM) { ax[p] *= um_mass; ay[p] *= um_mass; az[p] *= um_mass; }
-        if (li[p] < i_count) out[li[p]] = make_float4(ax[p].x, ay[p].x, az[p].x, 0.f);
-        if (li[p] + 1 < i_count) out[li[p] + 1] = make_float4(ax[p].y, ay[p].y, az[p].y, 0.f);
-    }
-}
 
 // ---------------------------------------------------------------------------
 // force_sym3_f32 — symmetric fast path in 3-D.  Same items / tiles / slab scheme as force_sym_f32
@@ -341,73 +233,6 @@ void force_sym3_f32(const float4 *__restrict__ pos, const SymItem *__restrict__ 
         out[li[p]] = make_float4(ax[p].x, ay[p].x, az[p].x, 0.f);
         out[li[p] + 1] = make_float4(ax[p].y, ay[p].y, az[p].y, 0.f);
     }
-}
-
-// ---------------------------------------------------------------------------
-// force_tiled3_f64 — one-sided 3-D kernel in double (one i per lane per register slot, like force_tiled_f64).
-// ---------------------------------------------------------------------------
-template <int P, bool GUARD, int UNROLL>
-__global__ __launch_bounds__(BLOCK)
-void force_tiled3_f64(const double4 *__restrict__ pos, double4 *__restrict__ partial,
-                      uint32_t i_begin, uint32_t i_count, uint32_t j_begin, uint32_t j_end,
-                      uint32_t js, uint32_t i_tiles, double eps2, uint32_t gap_begin, uint32_t gap_len)
-{
-    constexpr uint32_t IT = BLOCK * P;
-    __shared__ double4 tile[2][TJ];
-    const double k15 = vgpr_const(1.5), k1875 = vgpr_const(1.875);
-    const TileMap tm = decode_block(blockIdx.x, i_tiles, js);
-    if (!tm.valid) return;
-    const uint32_t t = threadIdx.x;
-    const uint32_t jn = j_end - j_begin;
-    const uint32_t slice_len = (((jn + js - 1) / js + TJ - 1) / TJ) * TJ;
-    const uint32_t s0 = j_begin + min(tm.slice * slice_len, jn);
-    const uint32_t s1 = j_begin + min((tm.slice + 1) * slice_len, jn);
-    double xi[P], yi[P], zi[P], ax[P], ay[P], az[P];
-    uint32_t li[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        li[p] = tm.i_tile * IT + (uint32_t)p * BLOCK + t;
-        const double4 p0 = pos[i_begin + min(li[p], i_count - 1)];
-        xi[p] = p0.x; yi[p] = p0.y; zi[p] = p0.z; ax[p] = ay[p] = az[p] = 0.0;
-    }
-    const uint32_t ntiles = (s1 - s0 + TJ - 1) / TJ;
-    const double4 none = make_double4(0.0, 0.0, 0.0, 0.0);        // mass 0: contributes nothing (eps > 0 or guarded)
-    {
-        const uint32_t j = s0 + t;
-        tile[0][t] = j < s1 ? pos[j + (j >= gap_begin ? gap_len : 0u)] : none;
-    }
-    __syncthreads();
-    for (uint32_t it = 0; it < ntiles; ++it) {
-        const uint32_t jn1 = s0 + (it + 1) * TJ + t;
-        const double4 qn = jn1 < s1 ? pos[jn1 + (jn1 >= gap_begin ? gap_len : 0u)] : none;
-        const double4 *__restrict__ cur = tile[it & 1];
-#pragma unroll UNROLL
-        for (int jj = 0; jj < TJ; ++jj) {
-            const double4 q = cur[jj];
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                const double dx = q.x - xi[p], dy = q.y - yi[p], dz = q.z - zi[p];
-                double r2, inv3;
-                if constexpr (GUARD) {
-                    r2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
-                    inv3 = r2 > 0.0 ? rsqrt3_f64(r2, k15, k1875) : 0.0;
-                } else {
-                    r2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2)));
-                    inv3 = rsqrt3_f64(r2, k15, k1875);
-                }
-                const double sc = q.w * inv3;
-                ax[p] = __builtin_fma(sc, dx, ax[p]);
-                ay[p] = __builtin_fma(sc, dy, ay[p]);
-                az[p] = __builtin_fma(sc, dz, az[p]);
-            }
-        }
-        if (it + 1 < ntiles) tile[(it + 1) & 1][t] = qn;
-        __syncthreads();
-    }
-    double4 *__restrict__ out = partial + (size_t)tm.slice * i_count;
-#pragma unroll
-    for (int p = 0; p < P; ++p)
-        if (li[p] < i_count) out[li[p]] = make_double4(ax[p], ay[p], az[p], 0.0);
 }
 
 // ---------------------------------------------------------------------------

@@ -5,6 +5,10 @@ final bodies compared bit for bit (sha256 of pos | vel | acc) and timed.  For ch
     git worktree add /tmp/old <commit> && make -C /tmp/old/nbodysim_amd/csrc && cp /tmp/old/nbodysim_amd/libnbody_hip.so build/old_lib/
     python tools/lib_ab.py --old build/old_lib/libnbody_hip.so [--cases p9216,p16384,ref25000,...]
 
+A case is [MODS-]BASE<n>.  BASE: p 2-D fp32, d 2-D fp64, q 3-D fp32, qd 3-D fp64, ref the reference start.  MODS, letters
+in any order: o one-sided (symmetry=False), g eps = 0 (the guarded body, one-sided), k rsqrt="quake", s mass scaling in the
+individual-masses run (uniform_mass=False, mass_scaling=True).  Example: og-qd4096, os-p65536.
+
 (the Python binding loads $NBODY_HIP_LIB when set — the LIBRARY reads no environment variables; each side runs in a child process)
 """
 import argparse
@@ -26,18 +30,29 @@ def child(cases, steps):
     import nbodysim_amd as nb
     out = {}
     for name in cases:
-        if name.startswith("ref"):
-            ic, kw, dt = nb.default_ics(int(name[3:])), dict(eps=1.0, extras=3), 0.01
-        elif name.startswith("q"):                   # 3-D
-            ic, kw, dt = nb.plummer_3d(int(name[1:]), 42), dict(eps=0.01, dims=3), 1e-3
-        elif name.startswith("d"):                   # fp64
-            ic, kw, dt = nb.plummer_2d(int(name[1:]), 42), dict(eps=0.01, precision="fp64"), 1e-3
+        mods, _, base = name.rpartition("-")
+        if base.startswith("ref"):
+            ic, kw, dt = nb.default_ics(int(base[3:])), dict(eps=1.0, extras=3), 0.01
+        elif base.startswith("qd"):                  # 3-D fp64
+            ic, kw, dt = nb.plummer_3d(int(base[2:]), 42), dict(eps=0.01, dims=3, precision="fp64"), 1e-3
+        elif base.startswith("q"):                   # 3-D
+            ic, kw, dt = nb.plummer_3d(int(base[1:]), 42), dict(eps=0.01, dims=3), 1e-3
+        elif base.startswith("d"):                   # fp64
+            ic, kw, dt = nb.plummer_2d(int(base[1:]), 42), dict(eps=0.01, precision="fp64"), 1e-3
         else:
-            ic, kw, dt = nb.plummer_2d(int(name[1:]), 42), dict(eps=0.01), 1e-3
+            ic, kw, dt = nb.plummer_2d(int(base[1:]), 42), dict(eps=0.01), 1e-3
+        if "o" in mods:
+            kw["symmetry"] = False
+        if "g" in mods:
+            kw["eps"] = 0.0
+        if "k" in mods:
+            kw["rsqrt"] = "quake"
         for general in (False, True):
             k = dict(kw)
             if general:
                 k["uniform_mass"] = False
+                if "s" in mods:
+                    k["mass_scaling"] = True
             with nb.Simulation(ic, **k) as s:
                 s.advance(30, dt)
                 s.wait()
