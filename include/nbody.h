@@ -33,7 +33,7 @@ extern "C" {
  * nb_* symbols; tests/test_abi.py).  Test hooks live in include/nbody_debug.h and exist only in a -DNB_TEST_HOOKS build. */
 #pragma GCC visibility push(default)
 
-#define NB_ABI_VERSION 7
+#define NB_ABI_VERSION 8
 
 /* ---- particle record -------------------------------------------------------
  * Bit-compatible with the reference's `struct alignas(16) Body`
@@ -108,6 +108,33 @@ enum { NB_EXTRA_VCLAMP   = 1,   /* |v| <= 1000,            Simulation.hpp:133-13
                                    synchronising call (nb_wait, nb_sync, nb_sync_positions, nb_snapshot_wait, nb_energy,
                                    nb_momentum, nb_collision_stats) returns NB_ENOMEM once, naming the frame and the pairs
                                    needed; nb_collide_capacity raises it */
+
+/* nb_params.force: how the accelerations are evaluated (ABI 8) */
+enum { NB_FORCE_DIRECT = 0,    /* every pair: the kernels this library is built around (default) */
+       NB_FORCE_TREE = 1 };    /* the reference's own algorithm: Barnes-Hut quadtree, Quadtree::build / Quadtree::acc
+                                  (Quadtree.hpp:35-93,113-170,236-258), opening parameter nb_params.theta.  Per force evaluation:
+                                  root cell = Quad::new_containing of all bodies; one position per leaf (coincident bodies share a
+                                  leaf, masses added in ascending index); a cell holding two different positions has its four
+                                  children; centres of mass summed over the children in quadrant order; every body walks the nodes
+                                  in pre-order and adds d * (mass * inv^3) for each node with size^2 < d^2 * theta^2 and d^2 > 0, whose
+                                  subtree it then skips; a leaf that is not accepted adds nothing (the reference's leaf ranges are
+                                  empty, the body's own leaf included).  With NB_RSQRT_QUAKE the result is the compiled reference's
+                                  bit for bit, whatever the order of the bodies; with NB_RSQRT_EXACT the same nodes are accepted and
+                                  the term uses the hardware rsqrt and FMA.  A body with mass == 0 is not inserted (it is still
+                                  accelerated and integrated); positions must be finite.
+                                  Unsharded 2-D fp32 kick-drift handles only (nb_create: NB_EINVAL otherwise, naming the
+                                  combination); any rsqrt_mode, any extras.  REFUSED with it: NB_FP64, dims = 3, NB_INTEGRATOR_KDK,
+                                  shard_world > 1, i_count < n, NB_FLAG_SHARD_SINGLE / _ALLREDUCE, NB_SUM_SEQUENTIAL.  IGNORED with
+                                  it (they select or shape the direct-sum launches, none of which a tree handle ever runs; range
+                                  checks still apply): NB_FLAG_NO_SYMMETRY, _NO_UNIFORM_MASS, _NO_GUIDED_TAIL, _MASS_SCALING,
+                                  _MASS_SCALING_MEASURED, _NO_MASS_SCALING, _STATIC_ITEMS, j_slices, lanes_p, the sym_* tuning fields
+                                  and acc_buffers.  Caller-owned pos_buffers are accepted as for any unsharded handle.
+                                  Device memory is O(n): no symmetric plan, slabs or partials.  Node capacity 16 n + 4096, paths are
+                                  followed for 63 levels; an evaluation that needs more integrates nothing (positions and velocities
+                                  stay; with NB_EXTRA_COLLIDE the collision pass of that step still runs, on the unchanged
+                                  positions), and the next synchronising call (nb_wait, nb_sync, nb_sync_positions, nb_energy,
+                                  nb_momentum, nb_tree_stats) returns NB_ENOMEM once, naming the frame and what was needed.
+                                  nb_energy / nb_momentum stay the exact O(n^2) / O(n) diagnostics */
 
 /* integrator */
 enum { NB_INTEGRATOR_KICK_DRIFT = 0, /* Simulation.hpp:129-131,160-163 (reference) */
@@ -212,6 +239,9 @@ typedef struct nb_params {
                                      not divide n all-gathers ceil(n / world) rows per rank, so its replicas need world * ceil(n / world)
                                      rows: replicas the library allocates itself are sized that way, caller-owned ones must be and say so
                                      here (rows past n are never read by the kernels) */
+    int32_t  force;               /* NB_FORCE_*; default NB_FORCE_DIRECT (ABI 8) */
+    float    theta;               /* NB_FORCE_TREE: opening parameter, >= 0 and finite; default 1.0f, the reference's
+                                     quadtree(1.0f, 1.0f, 16) (Simulation.hpp:59).  0 opens every branch */
 } nb_params;
 
 typedef struct nb_sim nb_sim; /* opaque; stands for one `Simulation` (Simulation.hpp:49) */
@@ -308,6 +338,11 @@ int nb_momentum(nb_sim *s, double *p_xyz, double *l_z);
 int nb_collide_capacity(nb_sim *s, size_t max_pairs);
 int nb_collision_stats(nb_sim *s, uint64_t *pairs_last_step, uint64_t *pairs_total, uint32_t *rounds_last_step,
                        uint64_t *overflow_steps);
+
+/* Barnes-Hut force (NB_FORCE_TREE).  nb_tree_stats synchronises and returns the nodes and the deepest leaf of the last force
+ * evaluation and the evaluations that failed (node capacity, depth cap) since creation; any pointer may be NULL; NB_ESTATE
+ * on a NB_FORCE_DIRECT handle. */
+int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, uint64_t *overflow_steps);
 
 /* Counters: Simulation::frame (Simulation.hpp:53) and sizes. */
 uint64_t nb_frame(const nb_sim *s);

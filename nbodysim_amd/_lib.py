@@ -17,7 +17,7 @@ import numpy as np
 PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = PKG_DIR / "libnbody_hip.so"
 
-NB_ABI_VERSION = 7
+NB_ABI_VERSION = 8
 
 # enums (include/nbody.h)
 NB_OK, NB_EINVAL, NB_ENODEVICE, NB_EHIP, NB_ENOMEM, NB_EIO, NB_EFORMAT, NB_ESTATE = 0, -1, -2, -3, -4, -5, -6, -7
@@ -26,6 +26,7 @@ NB_RSQRT_EXACT, NB_RSQRT_QUAKE = 0, 1
 NB_SUM_TILED, NB_SUM_SEQUENTIAL = 0, 1
 NB_EXTRA_VCLAMP, NB_EXTRA_BOUNDARY, NB_EXTRA_COLLIDE = 1, 2, 4
 NB_INTEGRATOR_KICK_DRIFT, NB_INTEGRATOR_KDK = 0, 1
+NB_FORCE_DIRECT, NB_FORCE_TREE = 0, 1
 NB_POS_CURRENT, NB_POS_NEXT = 0, 1
 NB_SHARD_NONE, NB_SHARD_ALLGATHER, NB_SHARD_SYMMETRIC, NB_SHARD_ALLREDUCE = 0, 1, 2, 3
 NB_FLAG_NO_SYMMETRY, NB_FLAG_NO_UNIFORM_MASS, NB_FLAG_NO_GUIDED_TAIL, NB_FLAG_SHARD_ALLREDUCE, NB_FLAG_SHARD_SINGLE, NB_FLAG_MASS_SCALING = 1, 2, 4, 8, 16, 32
@@ -94,6 +95,8 @@ class nb_params(C.Structure):
         ("sym_tile", C.c_int32),
         ("_reserved0", C.c_int32),
         ("pos_rows", C.c_uint64),
+        ("force", C.c_int32),
+        ("theta", C.c_float),
     ]
 
 
@@ -165,6 +168,7 @@ PROTOTYPES = {
     "nb_momentum": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nb_collide_capacity": (C.c_int, [C.c_void_p, C.c_size_t]),
     "nb_collision_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "nb_tree_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),
     "nb_owned_begin": (C.c_size_t, [C.c_void_p]),

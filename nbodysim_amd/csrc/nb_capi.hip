@@ -12,6 +12,7 @@
 #include "nb_kernels.hip.h"
 #include "nb_kernels3d.hip.h"
 #include "nb_collide.hip.h"
+#include "nb_tree.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -167,6 +168,29 @@ struct nb_sim {
     uint8_t *coll_sadv = nullptr;
     CollideStats *coll_stats = nullptr;        // device
     CollideStats *coll_host = nullptr;         // page-locked mirror
+
+    // Barnes-Hut force (NB_FORCE_TREE, nb_tree.hip.h): nothing below is allocated for a direct-sum handle
+    bool tree = false;
+    float tree_theta2 = 1.0f;                  // theta * theta, Quadtree.hpp:18
+    uint64_t tree_cap = 0;                     // node capacity: nodes allocated
+    uint64_t tree_ovf_reported = 0;            // failed evaluations already reported by a synchronising call
+    uint64_t *tree_k64[4] = {nullptr, nullptr, nullptr, nullptr};   // key words by body: high, low; two sort buffers
+    uint32_t *tree_v32[3] = {nullptr, nullptr, nullptr};            // body indices: identity, after the low-word sort, sorted
+    uint32_t *tree_head = nullptr;                                  // n + 1: key starts ...
+    uint64_t *tree_uidx = nullptr;                                  // ... and their prefix sum
+    uint64_t *tree_uhi = nullptr, *tree_ulo = nullptr;              // keys of the points (different positions)
+    uint32_t *tree_ufirst = nullptr;                                // first sorted position of every point
+    uint32_t *tree_cnt = nullptr;                                   // n + 2: nodes per point ...
+    uint64_t *tree_base = nullptr;                                  // ... and their prefix sum (64-bit: 440 nodes per point x 2^31 bodies)
+    float4 *tree_part = nullptr;               // bounds partials
+    TreeRoot *tree_root_dev = nullptr;
+    float4 *tree_nd = nullptr;                 // node records {com.x, com.y, mass, size^2}
+    uint32_t *tree_nx = nullptr;               // next: index + subtree size
+    uint8_t *tree_dp = nullptr;                // depth | TREE_BRANCH
+    void *tree_tmp = nullptr;                  // rocprim temporary storage (sort, scan)
+    size_t tree_tmp_bytes = 0;
+    TreeStats *tree_stats = nullptr;           // device
+    TreeStats *tree_host = nullptr;            // page-locked mirror
 
     // profiling
     bool prof = false;
@@ -341,6 +365,7 @@ static bool single_rank(const nb_sim *s)
 static StepPath step_path_of(const nb_sim *s)
 {
     const bool whole = s->i_count == s->n;
+    if (s->p.force == NB_FORCE_TREE) return StepPath::ONE_SIDED;      // its force launch is launch_tree_force
     if (sym_eligible(s)) {
         const bool kick_drift = s->p.integrator == NB_INTEGRATOR_KICK_DRIFT, allreduce = (s->p.flags & NB_FLAG_SHARD_ALLREDUCE) != 0;
         const size_t w = (size_t)s->p.shard_world;
@@ -660,6 +685,12 @@ static void free_all(nb_sim *s)
                     (void *)s->coll_bits, (void *)s->coll_chunk_e, (void *)s->coll_chunk_t, s->coll_spos, s->coll_svel, (void *)s->coll_scur, (void *)s->coll_sadv, (void *)s->coll_stats})
         (void)hipFree(q);
     if (s->coll_host) (void)hipHostFree(s->coll_host);
+    for (void *q : {(void *)s->tree_k64[0], (void *)s->tree_k64[1], (void *)s->tree_k64[2], (void *)s->tree_k64[3], (void *)s->tree_v32[0],
+                    (void *)s->tree_v32[1], (void *)s->tree_v32[2], (void *)s->tree_head, (void *)s->tree_uidx, (void *)s->tree_uhi,
+                    (void *)s->tree_ulo, (void *)s->tree_ufirst, (void *)s->tree_cnt, (void *)s->tree_base, (void *)s->tree_part,
+                    (void *)s->tree_root_dev, (void *)s->tree_nd, (void *)s->tree_nx, (void *)s->tree_dp, s->tree_tmp, (void *)s->tree_stats})
+        (void)hipFree(q);
+    if (s->tree_host) (void)hipHostFree(s->tree_host);
     if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
     if (s->ev_packed) (void)hipEventDestroy(s->ev_packed);
     if (s->ev_copied) (void)hipEventDestroy(s->ev_copied);
@@ -893,6 +924,125 @@ static int collide_check(nb_sim *s)
     return rc ? rc : collide_report(s);
 }
 
+// ---------------------------------------------------------------------------
+// Barnes-Hut force (NB_FORCE_TREE): host side of nb_tree.hip.h
+// ---------------------------------------------------------------------------
+static int prof_begin(nb_sim *s, std::pair<hipEvent_t, hipEvent_t> *pr, hipStream_t st);
+static int prof_end(nb_sim *s, const std::pair<hipEvent_t, hipEvent_t> &pr, hipStream_t st, uint32_t passes);
+
+// Node capacity: 16 n + 4096.  Measured (DESIGN.md "Barnes-Hut force"): the reference's default bodies need 2.8 n nodes, Plummer
+// spheres of 1 048 576 and 8 388 608 bodies 2.9 n; a pair of bodies much closer than its neighbours adds four nodes per level it
+// takes to part them (the 256 isolated touching pairs of tests/golden/collide_isolated_ic.npy: 10.2 n).
+static int tree_alloc(nb_sim *s)
+{
+    const size_t n = s->n;
+    s->tree_cap = std::min<uint64_t>(16 * (uint64_t)n + 4096, 0xfffffff0u);
+    for (auto &q : s->tree_k64) HIPCHK(hipMalloc((void **)&q, n * sizeof(uint64_t)));
+    for (auto &q : s->tree_v32) HIPCHK(hipMalloc((void **)&q, n * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_head, (n + 1) * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_uidx, (n + 1) * sizeof(uint64_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_uhi, n * sizeof(uint64_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_ulo, n * sizeof(uint64_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_ufirst, n * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_cnt, (n + 2) * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_base, (n + 2) * sizeof(uint64_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_part, TREE_BOUNDS_BLOCKS * sizeof(float4)));
+    HIPCHK(hipMalloc((void **)&s->tree_root_dev, sizeof(TreeRoot)));
+    HIPCHK(hipMalloc((void **)&s->tree_nd, s->tree_cap * sizeof(float4)));
+    HIPCHK(hipMalloc((void **)&s->tree_nx, s->tree_cap * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_dp, s->tree_cap));
+    size_t sort_bytes = 0, scan_bytes = 0;
+    HIPCHK(nb_tree_sort_pairs(nullptr, sort_bytes, s->tree_k64[0], s->tree_k64[2], s->tree_v32[0], s->tree_v32[1], n, s->stream));
+    HIPCHK(nb_tree_scan(nullptr, scan_bytes, s->tree_cnt, s->tree_base, n + 2, s->stream));
+    s->tree_tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 256);
+    HIPCHK(hipMalloc(&s->tree_tmp, s->tree_tmp_bytes));
+    HIPCHK(hipMalloc((void **)&s->tree_stats, sizeof(TreeStats)));
+    HIPCHK(hipHostMalloc((void **)&s->tree_host, sizeof(TreeStats), hipHostMallocDefault));
+    HIPCHK(hipMemsetAsync(s->tree_stats, 0, sizeof(TreeStats), s->stream));
+    memset(s->tree_host, 0, sizeof(TreeStats));
+    return NB_OK;
+}
+
+// One force evaluation at pos[cur] into acc[] (nb_tree.hip.h has the pipeline).  The walk is "the force kernel" of nb_profile_read.
+static int launch_tree_force(nb_sim *s)
+{
+    const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u, g2 = (n + 2u + 255u) / 256u;
+    const float2 *pos = (const float2 *)s->pos[s->cur];
+    const float *mass = (const float *)s->mass;
+    uint64_t *khi = s->tree_k64[0], *klo = s->tree_k64[1], *ka = s->tree_k64[2], *kb = s->tree_k64[3];
+    uint32_t *v0 = s->tree_v32[0], *v1 = s->tree_v32[1], *v2 = s->tree_v32[2];
+    TreeStats *st = s->tree_stats;
+    size_t tmp = s->tree_tmp_bytes;
+    tree_bounds<<<std::min(g, TREE_BOUNDS_BLOCKS), 256, 0, s->stream>>>(pos, n, s->tree_part);
+    tree_root<<<1, 256, 0, s->stream>>>(s->tree_part, std::min(g, TREE_BOUNDS_BLOCKS), s->tree_root_dev, st);
+    tree_keys<<<g, 256, 0, s->stream>>>(pos, mass, n, s->tree_root_dev, khi, klo, v0, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(nb_tree_sort_pairs(s->tree_tmp, tmp, klo, ka, v0, v1, n, s->stream));          // by the low word ...
+    tree_gather_hi<<<g, 256, 0, s->stream>>>(khi, v1, n, kb);
+    HIPCHK(nb_tree_sort_pairs(s->tree_tmp, tmp, kb, ka, v1, v2, n, s->stream));           // ... then, stable, by the high one
+    tree_heads<<<g2, 256, 0, s->stream>>>(ka, klo, v2, pos, n, s->tree_head, st, s->frame);
+    HIPCHK(hipGetLastError());
+    HIPCHK(nb_tree_scan(s->tree_tmp, tmp, s->tree_head, s->tree_uidx, (size_t)n + 1, s->stream));
+    tree_points<<<g2, 256, 0, s->stream>>>(ka, klo, v2, s->tree_head, s->tree_uidx, n, s->tree_uhi, s->tree_ulo, s->tree_ufirst, st);
+    tree_count<<<g2, 256, 0, s->stream>>>(s->tree_uhi, s->tree_ulo, n, s->tree_cnt, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(nb_tree_scan(s->tree_tmp, tmp, s->tree_cnt, s->tree_base, (size_t)n + 2, s->stream));
+    tree_emit<<<g2, 256, 0, s->stream>>>(s->tree_uhi, s->tree_ulo, s->tree_ufirst, v2, pos, mass, s->tree_base, n, s->tree_root_dev, s->tree_cap,
+                                         s->tree_nd, s->tree_nx, s->tree_dp, st, s->frame);
+    const uint32_t gc = (uint32_t)std::min<uint64_t>((s->tree_cap + 255u) / 256u, 8u * (uint32_t)s->cus);
+    for (int level = TREE_DEPTH_CAP - 1; level >= 0; --level)
+        tree_com<<<gc, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, (uint32_t)level, st);
+    HIPCHK(hipGetLastError());
+    std::pair<hipEvent_t, hipEvent_t> pr;
+    if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
+    const float eps2 = s->p.eps * s->p.eps;
+    with_flags([&](auto q) {
+        tree_walk<q ? RSQ_QUAKE : RSQ_EXACT><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st);
+    }, s->p.rsqrt_mode == NB_RSQRT_QUAKE);
+    HIPCHK(hipGetLastError());
+    if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
+    return NB_OK;
+}
+
+// acc[] of the tree walk -> kick, drift (or acc only): the reference-order form with the Quake rsqrt, the fused one otherwise
+static int launch_tree_integrate(nb_sim *s, double dt_kick, double dt_drift, int flags)
+{
+    const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u;
+    using L2 = Layout<float, false>;
+    with_flags([&](auto strict) {
+        tree_integrate<L2, strict><<<g, 256, 0, s->stream>>>((const float2 *)s->pos[s->cur], (float2 *)s->pos[s->cur ^ 1], (float2 *)s->vel,
+                                                              (float2 *)s->acc, n, (float)dt_kick, (float)dt_drift, s->p.extras, flags, s->tree_stats);
+    }, s->p.rsqrt_mode == NB_RSQRT_QUAKE);
+    HIPCHK(hipGetLastError());
+    return NB_OK;
+}
+
+// A failed build (node capacity, depth cap) is reported ONCE, by the first synchronising call after it, like a collision overflow.
+static int tree_check(nb_sim *s)
+{
+    if (!s->tree) return NB_OK;
+    HIPCHK(hipMemcpyAsync(s->tree_host, s->tree_stats, sizeof(TreeStats), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const TreeStats &t = *s->tree_host;
+    if (t.overflow_steps <= s->tree_ovf_reported) return NB_OK;
+    const unsigned long long steps = (unsigned long long)(t.overflow_steps - s->tree_ovf_reported);
+    s->tree_ovf_reported = t.overflow_steps;
+    if (t.overflow_kind == 1)
+        return nb_fail(NB_ENOMEM, "tree: the force evaluation at frame %llu needed %llu nodes, more than the capacity of %llu; nothing was "
+                                  "integrated (%llu evaluation(s) failed since the last report)",
+                       (unsigned long long)t.overflow_frame, (unsigned long long)t.overflow_needed, (unsigned long long)s->tree_cap, steps);
+    return nb_fail(NB_ENOMEM, "tree: at frame %llu two different positions (sorted position %llu) are not separated within %d levels; nothing "
+                              "was integrated (%llu evaluation(s) failed since the last report)",
+                   (unsigned long long)t.overflow_frame, (unsigned long long)t.overflow_needed, TREE_DEPTH_CAP, steps);
+}
+
+// what every synchronising call reports once: a collision step over capacity, a failed tree build
+static int step_check(nb_sim *s)
+{
+    const int rc = collide_check(s);
+    return rc ? rc : tree_check(s);
+}
+
 static int snapshot_wait(nb_sim *s);
 
 static int do_upload(nb_sim *s, const nb_body *in)
@@ -900,7 +1050,8 @@ static int do_upload(nb_sim *s, const nb_body *in)
     { const int rc = fence_foreign_work(s); if (rc) return rc; }
     // Equal masses (the synthetic Plummer workload, most N-body ICs) let the force kernel hoist the
     // per-pair mass multiply: 8 instead of 9 packed ops per two pairs.  NB_FLAG_NO_UNIFORM_MASS disables it.
-    s->uniform_mass = s->n > 0 && !(s->p.flags & NB_FLAG_NO_UNIFORM_MASS) && s->p.sum_order == NB_SUM_TILED;
+    // (a tree handle has none of the direct-sum specialisations: the flags that select them are ignored, include/nbody.h)
+    s->uniform_mass = s->n > 0 && !s->tree && !(s->p.flags & NB_FLAG_NO_UNIFORM_MASS) && s->p.sum_order == NB_SUM_TILED;
     for (size_t i = 1; s->uniform_mass && i < s->n; ++i)
         if (memcmp(&in[i].mass, &in[0].mass, sizeof(float)) != 0) s->uniform_mass = false;
     s->um_mass = in[0].mass;
@@ -915,7 +1066,7 @@ static int do_upload(nb_sim *s, const nb_body *in)
     s->mass_scaled = false;
     s->mass_scaling_dev = -1.0f;
     bool scalable = false;
-    if (!s->uniform_mass && s->p.sum_order == NB_SUM_TILED && !needs_guard(s) && !s->fp64 && !s->dims3 &&
+    if (!s->tree && !s->uniform_mass && s->p.sum_order == NB_SUM_TILED && !needs_guard(s) && !s->fp64 && !s->dims3 &&
         s->p.rsqrt_mode == NB_RSQRT_EXACT && (s->p.flags & (NB_FLAG_MASS_SCALING | NB_FLAG_MASS_SCALING_MEASURED)) && !(s->p.flags & NB_FLAG_NO_MASS_SCALING)) {
         double mmin = HUGE_VAL, mmax = 0.0;
         bool finite = true;
@@ -992,6 +1143,18 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
             return nullptr;
         }
     }
+    if (p.force != NB_FORCE_DIRECT && p.force != NB_FORCE_TREE) { nb_set_error("nb_create: bad force %d", p.force); return nullptr; }
+    if (!(p.theta >= 0.0f) || !std::isfinite(p.theta)) { nb_set_error("nb_create: theta must be >= 0 and finite"); return nullptr; }
+    if (p.force == NB_FORCE_TREE) {
+        const char *why = p.precision == NB_FP64 ? "NB_FP64" : p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
+                        : p.shard_world > 1 ? "shard_world > 1" : (p.i_count != 0 && p.i_count < n) ? "i_count < n"
+                        : (p.flags & (NB_FLAG_SHARD_SINGLE | NB_FLAG_SHARD_ALLREDUCE)) ? "NB_FLAG_SHARD_SINGLE / NB_FLAG_SHARD_ALLREDUCE"
+                        : p.sum_order != NB_SUM_TILED ? "NB_SUM_SEQUENTIAL (the walk has one order: the reference's)" : nullptr;
+        if (why) {
+            nb_set_error("nb_create: the Barnes-Hut force (NB_FORCE_TREE) needs an unsharded 2-D fp32 kick-drift handle; not supported with %s", why);
+            return nullptr;
+        }
+    }
     if (p.sym_chunks_per_item < 0 || p.sym_aux_stream < -1 || p.sym_aux_stream > 1 || p.j_slices < 0 || p.sym_chunk_pairs < -1 || p.sym_chunk_pairs > 1 ||
         (p.sym_tile != 0 && p.sym_tile != (int32_t)SYM_SB_WS && p.sym_tile != (int32_t)SYM_SB) ||
         (p.lanes_p != 0 && p.lanes_p != 1 && p.lanes_p != 2 && p.lanes_p != 4) || !(p.sym_late_us == p.sym_late_us)) {
@@ -1064,11 +1227,14 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
         }
     }
     s->slabs_cap = s->slabs_all > s->slabs_two_phase ? s->slabs_all : s->slabs_two_phase;
+    s->tree = p.force == NB_FORCE_TREE;
+    s->tree_theta2 = p.theta * p.theta;
     if ((e = hipMalloc(&s->mass, n * s->rsz)) != hipSuccess) return fail("hipMalloc mass", e);
     if ((e = hipMalloc((void **)&s->radius, n * sizeof(float))) != hipSuccess) return fail("hipMalloc radius", e);
     if ((e = hipMalloc(&s->vel, s->i_count * r2)) != hipSuccess) return fail("hipMalloc vel", e);
     if ((e = hipMalloc(&s->acc, s->i_count * r2)) != hipSuccess) return fail("hipMalloc acc", e);
-    if ((e = hipMalloc(&s->partial, (size_t)s->slabs_cap * s->i_count * r2)) != hipSuccess) return fail("hipMalloc partial", e);
+    // (a tree handle has no one-sided partials: its walk writes acc[] itself)
+    if ((e = hipMalloc(&s->partial, s->tree ? r2 : (size_t)s->slabs_cap * s->i_count * r2)) != hipSuccess) return fail("hipMalloc partial", e);
     if ((e = hipMalloc((void **)&s->aos_dev, n * sizeof(nb_body))) != hipSuccess) return fail("hipMalloc aos", e);
     s->ered_blocks = (s->i_count + BLOCK - 1) / BLOCK;
     if ((e = hipMalloc((void **)&s->ered_dev, 2 * s->ered_blocks * sizeof(double))) != hipSuccess) return fail("hipMalloc energy", e);
@@ -1076,6 +1242,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     if (symmetric(s) && plan_sym(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
     s->collide = (p.extras & NB_EXTRA_COLLIDE) != 0;
     if (s->collide && collide_alloc(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
+    if (s->tree && tree_alloc(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
     if (do_upload(s, init) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
     return s;
 }
@@ -1264,6 +1431,7 @@ static int launch_force_sym(nb_sim *s, bool fuse_step = false, double dt = 0.0)
 static int launch_force(nb_sim *s, const ForceJob &j)
 {
     if (j.j_end <= j.j_begin || j.js == 0) return NB_OK;
+    if (s->tree) return nb_fail(NB_ESTATE, "internal: a direct-sum force launch on a NB_FORCE_TREE handle (it has no partial slabs)");
     if (s->path == StepPath::SYM && &j == &s->job_all) return launch_force_sym(s);
     std::pair<hipEvent_t, hipEvent_t> pr;
     if (s->prof && prof_begin(s, &pr)) return NB_EHIP;
@@ -1337,6 +1505,7 @@ static int launch_integrate(nb_sim *s, const void *src, uint32_t nslabs, uint32_
 // The one-sided form: the force partials of the owned block.
 static int integrate_slabs(nb_sim *s, uint32_t nslabs, double dt_kick, double dt_drift, int flags)
 {
+    if (s->tree) return nb_fail(NB_ESTATE, "internal: a slab integration on a NB_FORCE_TREE handle (it has no partial slabs)");
     return launch_integrate(s, s->partial, nslabs, (uint32_t)s->i_begin, (uint32_t)s->i_count, dt_kick, dt_drift, flags);
 }
 
@@ -1443,6 +1612,7 @@ extern "C" int nb_step_finish(nb_sim *s)
         if ((rc = launch_force(s, s->job_remote)) || (rc = integrate_slabs(s, s->slabs_two_phase, dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc;
         break;
     case StepPath::ONE_SIDED:
+        if (s->tree) { if ((rc = launch_tree_force(s)) || (rc = launch_tree_integrate(s, dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc; break; }
         if ((rc = launch_force(s, s->job_all)) || (rc = integrate_slabs(s, s->slabs_all, dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc;
         break;
     }
@@ -1500,6 +1670,7 @@ extern "C" int nb_accelerations(nb_sim *s)
     if (s->in_step) return nb_fail(NB_ESTATE, "nb_accelerations: a split step is in flight");
     if (bind(s)) return NB_EHIP;
     int rc;
+    if (s->tree) return (rc = launch_tree_force(s)) ? rc : launch_tree_integrate(s, 0.0, 0.0, 0);
     // job_all: a sharded or replicated handle has no whole-system plan, so this takes the one-sided kernels
     if ((rc = launch_force(s, s->job_all))) return rc;
     return integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0);   // acc <- sum of slabs, nothing else
@@ -1511,7 +1682,7 @@ extern "C" int nb_wait(nb_sim *s)
     if (bind(s)) return NB_EHIP;
     if (s->aux) HIPCHK(hipStreamSynchronize(s->aux));
     HIPCHK(hipStreamSynchronize(s->stream));
-    return collide_check(s);
+    return step_check(s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1656,7 +1827,7 @@ extern "C" int nb_sync(nb_sim *s, nb_body *out)
     if (!s || !out) return nb_fail(NB_EINVAL, "nb_sync: NULL argument");
     if (bind(s)) return NB_EHIP;
     int rc = snapshot_wait(s);                        // aos_dev / staging may still be feeding a pipelined snapshot
-    if (rc || (rc = collide_check(s))) return rc;
+    if (rc || (rc = step_check(s))) return rc;
     const size_t bytes = s->i_count * sizeof(nb_body);
     const bool direct = pinned_covers(out, bytes);
     if (!direct && ensure_staging(s)) return NB_EHIP;
@@ -1690,7 +1861,7 @@ extern "C" int nb_sync_positions(nb_sim *s, float *out_xy)
     if (!s || !out_xy) return nb_fail(NB_EINVAL, "nb_sync_positions: NULL argument");
     if (bind(s)) return NB_EHIP;
     if (snapshot_wait(s)) return nb_last_error_code();
-    { const int rc = collide_check(s); if (rc) return rc; }
+    { const int rc = step_check(s); if (rc) return rc; }
     if (ensure_staging(s)) return NB_EHIP;
     const uint32_t ic = (uint32_t)s->i_count, g = (ic + BLOCK - 1) / BLOCK;
     const size_t bytes = s->i_count * (s->dims3 ? 3 : 2) * sizeof(float);       // (x, y) or (x, y, z) per body
@@ -1712,7 +1883,7 @@ extern "C" int nb_energy(nb_sim *s, double *kinetic, double *potential)
 {
     if (!s || !kinetic || !potential) return nb_fail(NB_EINVAL, "nb_energy: NULL argument");
     if (bind(s)) return NB_EHIP;
-    { const int rc = collide_check(s); if (rc) return rc; }
+    { const int rc = step_check(s); if (rc) return rc; }
     const uint32_t g = (uint32_t)s->ered_blocks;
     const double eps2 = (double)s->p.eps * (double)s->p.eps;
     with_layout(s, [&](auto L) {
@@ -1736,7 +1907,7 @@ extern "C" int nb_momentum(nb_sim *s, double *p_xyz, double *l_z)
 {
     if (!s || !p_xyz) return nb_fail(NB_EINVAL, "nb_momentum: NULL argument");
     if (bind(s)) return NB_EHIP;
-    { const int rc = collide_check(s); if (rc) return rc; }
+    { const int rc = step_check(s); if (rc) return rc; }
     const uint32_t g = (uint32_t)s->ered_blocks;
     if (!s->pred_dev) HIPCHK(hipMalloc((void **)&s->pred_dev, 4 * (size_t)g * sizeof(double)));
     with_layout(s, [&](auto L) {
@@ -1784,6 +1955,19 @@ extern "C" int nb_collision_stats(nb_sim *s, uint64_t *pairs_last_step, uint64_t
     if (pairs_total) *pairs_total = c.pairs_total;
     if (rounds_last_step) *rounds_last_step = c.rounds_last;
     if (overflow_steps) *overflow_steps = c.overflow_steps;
+    return rc;
+}
+
+extern "C" int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, uint64_t *overflow_steps)
+{
+    if (!s) return nb_fail(NB_EINVAL, "nb_tree_stats: NULL handle");
+    if (!s->tree) return nb_fail(NB_ESTATE, "nb_tree_stats: the handle was created with NB_FORCE_DIRECT");
+    if (bind(s)) return NB_EHIP;
+    const int rc = tree_check(s);
+    if (rc && nb_last_error_code() != NB_ENOMEM) return rc;
+    if (nodes) *nodes = s->tree_host->nodes;
+    if (max_depth) *max_depth = s->tree_host->max_depth;
+    if (overflow_steps) *overflow_steps = s->tree_host->overflow_steps;
     return rc;
 }
 
@@ -2054,5 +2238,11 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
     if (used >= 0 && (size_t)used < buflen)
         snprintf(buf + used, buflen - (size_t)used, " | collide=%d h=%.6g large=%u capacity=%llu resolve=%s", (int)s->collide, s->coll_h,
                  s->coll_large_n, (unsigned long long)s->coll_cap, resolve);
+    const size_t len = strlen(buf);
+    if (len < buflen) {
+        if (s->tree) snprintf(buf + len, buflen - len, " | force=tree theta=%.6g node_capacity=%llu depth_cap=%d", (double)s->p.theta,
+                              (unsigned long long)s->tree_cap, TREE_DEPTH_CAP);
+        else snprintf(buf + len, buflen - len, " | force=direct");
+    }
     return NB_OK;
 }

@@ -62,6 +62,8 @@ void nb_params_default(nb_params *p)
     p->extras = 0;
     p->device = -1;
     p->dims = 2;
+    p->force = NB_FORCE_DIRECT;
+    p->theta = 1.0f; /* Simulation.hpp:59  quadtree(1.0f, 1.0f, 16) */
 }
 
 /* ---- mt19937 (Matsumoto & Nishimura 1998), same stream as std::mt19937(seed),

@@ -1,0 +1,400 @@
+// nb_tree.hip.h — Barnes-Hut force (NB_FORCE_TREE, include/nbody.h): the reference's Quadtree::build / Quadtree::acc
+// (Quadtree.hpp:35-93,113-170,236-258) as a parallel build that produces the SAME cells, centres of mass and visit order,
+// so that with RSQ_QUAKE every body sees the reference's arithmetic bit for bit (tests/tree_model.py is the CPU statement).
+//
+// Why a parallel build can be exact: with one body per leaf the reference's tree does not depend on the insertion order —
+// a cell is a branch exactly when it holds two different positions, a branch has its four children in quadrant order, the
+// walk is a pre-order traversal and a branch sums its children 0..3.  Only node INDICES depend on the order.
+//
+// One force evaluation (all on the handle's stream, no host synchronisation, no floating-point atomics):
+//   tree_bounds / tree_root   min / max of the positions -> root cell, cell size^2 per depth, per-step counters reset
+//   tree_keys                 one thread per body descends TREE_DEPTH_CAP levels with the reference's rounded child centres
+//                             (Quad.hpp:47-57) and packs the quadrants taken into a 126-bit key (2 bits per level, most
+//                             significant first; the top bit marks a massless body, which is not inserted and sorts last)
+//   2 x rocprim radix sort    bodies by (key, body index): low word, then stable by the high word (nb_tree_prims.hip)
+//   tree_heads + scan         equal keys = one position = one leaf ("point"); two DIFFERENT positions with equal keys are
+//                             not separated within the cap: the build fails (reported like a collision overflow)
+//   tree_count + scan         nodes each point contributes to the pre-order layout (below) -> its first node index
+//   tree_emit                 writes the nodes: record {com.x, com.y, mass, size^2}, next (= index + subtree size), depth
+//   tree_com (per level)      centres of mass bottom-up, children 0..3 in order (Quadtree.hpp:236-258)
+//   tree_walk                 Quadtree::acc per body, bodies in key order so that a wave's lanes walk neighbouring paths
+//   tree_integrate            kick_drift_one (nb_kernels.hip.h) unless the build failed
+//
+// Pre-order layout from the sorted points.  Let L(u) be the number of leading levels points u and u + 1 share (-1 past
+// either end) and d(u) = max(L(u - 1), L(u)) + 1 the depth of point u's leaf.  Between leaf u - 1 and leaf u the traversal
+//   leaves the cells of depth d(u-1) - 1 ... L(u-1) + 1 of point u - 1: the quadrants after its own are empty leaves;
+//   at their common cell (depth L(u-1)) passes the empty quadrants between the two;
+//   enters the cells of depth L(u-1) + 1 ... d(u) - 1 of point u: a branch, then the empty quadrants before u's own;
+//   and reaches leaf u.
+// Point u writes exactly these nodes (point 0 starts at the root, a virtual point U closes the cells of the last one), so
+// a prefix sum of the counts gives every point its first index.  A branch ends where its last point's closing run ends.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "nb_tree_prims.h"
+
+namespace nbk {
+
+// Levels a path is followed for.  Measured leaf depths (nb_tree_stats; DESIGN.md has the runs): the reference's 25 000 default
+// bodies 16, Plummer spheres of 1 048 576 bodies 23 and of 8 388 608 bodies 28.
+constexpr int TREE_DEPTH_CAP = 63;
+constexpr int TREE_HI_LEVELS = 31;                 // levels 0..30 in the high word (bit 63 = massless), 31..62 in the low word
+constexpr uint64_t TREE_MASSLESS = 1ull << 63;
+constexpr uint32_t TREE_BOUNDS_BLOCKS = 1024;
+
+struct TreeStats {
+    uint32_t fail;               // this evaluation: 0 ok, 1 node capacity, 2 depth cap
+    uint32_t massive;            // bodies inserted (mass != 0)
+    uint32_t points;             // different positions among them
+    uint32_t max_depth;          // deepest leaf of this evaluation
+    uint64_t nodes;              // nodes of this evaluation (needed, also when over capacity)
+    uint64_t overflow_steps;     // evaluations that failed since creation
+    uint64_t overflow_frame;     // frame counter of the last one
+    uint64_t overflow_needed;    // nodes it needed (capacity) / sorted position of the unseparated pair (depth)
+    uint32_t overflow_kind;      // its `fail` value
+    uint32_t _pad;
+};
+
+struct TreeRoot { float cx, cy, size, _pad; float s2[TREE_DEPTH_CAP + 1]; };
+
+__device__ __forceinline__ uint32_t tree_digit(uint64_t hi, uint64_t lo, int l)
+{
+    return l < TREE_HI_LEVELS ? (uint32_t)(hi >> (60 - 2 * l)) & 3u : (uint32_t)(lo >> (62 - 2 * (l - TREE_HI_LEVELS))) & 3u;
+}
+
+// leading levels two DIFFERENT keys of inserted bodies share
+__device__ __forceinline__ int tree_lcp(uint64_t ah, uint64_t al, uint64_t bh, uint64_t bl)
+{
+    const uint64_t x = ah ^ bh;
+    if (x) return (__clzll((long long)x) - 2) >> 1;
+    return TREE_HI_LEVELS + (__clzll((long long)(al ^ bl)) >> 1);
+}
+
+// ---- bounds ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void tree_bounds(const float2 *__restrict__ pos, uint32_t n, float4 *__restrict__ part)
+{
+    __shared__ float4 sh[256];
+    float lx = 3.402823466e38f, ly = lx, hx = -lx, hy = -lx;        // Quad.hpp:32-33
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const float2 p = pos[i];
+        lx = fminf(lx, p.x); ly = fminf(ly, p.y); hx = fmaxf(hx, p.x); hy = fmaxf(hy, p.y);
+    }
+    sh[threadIdx.x] = make_float4(lx, ly, hx, hy);
+    __syncthreads();
+    for (uint32_t s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            const float4 a = sh[threadIdx.x], b = sh[threadIdx.x + s];
+            sh[threadIdx.x] = make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
+}
+
+__global__ __launch_bounds__(256)
+void tree_root(const float4 *__restrict__ part, uint32_t blocks, TreeRoot *__restrict__ root, TreeStats *__restrict__ st)
+{
+#pragma clang fp contract(off)
+    __shared__ float4 sh[256];
+    float lx = 3.402823466e38f, ly = lx, hx = -lx, hy = -lx;
+    for (uint32_t i = threadIdx.x; i < blocks; i += 256u) {
+        const float4 p = part[i];
+        lx = fminf(lx, p.x); ly = fminf(ly, p.y); hx = fmaxf(hx, p.z); hy = fmaxf(hy, p.w);
+    }
+    sh[threadIdx.x] = make_float4(lx, ly, hx, hy);
+    __syncthreads();
+    for (uint32_t s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            const float4 a = sh[threadIdx.x], b = sh[threadIdx.x + s];
+            sh[threadIdx.x] = make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float4 b = sh[0];
+        root->cx = (b.x + b.z) * 0.5f;                               // Quad.hpp:40-44
+        root->cy = (b.y + b.w) * 0.5f;
+        const float ex = b.z - b.x, ey = b.w - b.y;
+        float size = ex > ey ? ex : ey;
+        root->size = size;
+        for (int l = 0; l <= TREE_DEPTH_CAP; ++l) { root->s2[l] = size * size; size = size * 0.5f; }
+        st->fail = 0; st->massive = 0; st->points = 0; st->max_depth = 0; st->nodes = 0;
+    }
+}
+
+// ---- path keys ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void tree_keys(const float2 *__restrict__ pos, const float *__restrict__ mass, uint32_t n, const TreeRoot *__restrict__ root,
+               uint64_t *__restrict__ khi, uint64_t *__restrict__ klo, uint32_t *__restrict__ val, TreeStats *__restrict__ st)
+{
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool inserted = i < n && mass[i] != 0.0f;
+    const uint64_t wave = __ballot(inserted);                                 // one counter update per wave
+    if ((threadIdx.x & 63u) == 0 && wave) atomicAdd(&st->massive, (uint32_t)__popcll(wave));
+    if (i >= n) return;
+    val[i] = i;
+    if (!inserted) { khi[i] = TREE_MASSLESS; klo[i] = 0; return; }
+    const float2 p = pos[i];
+    float cx = root->cx, cy = root->cy, size = root->size;
+    uint64_t hi = 0, lo = 0;
+    for (int l = 0; l < TREE_DEPTH_CAP; ++l) {
+        const uint32_t qx = p.x > cx ? 1u : 0u, qy = p.y > cy ? 1u : 0u;      // Quad.hpp:47-49
+        const uint64_t q = (uint64_t)((qy << 1) | qx);
+        if (l < TREE_HI_LEVELS) hi |= q << (60 - 2 * l); else lo |= q << (62 - 2 * (l - TREE_HI_LEVELS));
+        size = size * 0.5f;                                                   // Quad.hpp:51-57
+        cx = cx + ((float)qx - 0.5f) * size;
+        cy = cy + ((float)qy - 0.5f) * size;
+    }
+    khi[i] = hi; klo[i] = lo;
+}
+
+__global__ __launch_bounds__(256)
+void tree_gather_hi(const uint64_t *__restrict__ khi, const uint32_t *__restrict__ val, uint32_t n, uint64_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) out[i] = khi[val[i]];
+}
+
+// ---- points ---------------------------------------------------------------------------------------------------------
+// head[i] = 1 where sorted position i starts a new key (i < massive); head[n] = 0 closes the scan.
+__global__ __launch_bounds__(256)
+void tree_heads(const uint64_t *__restrict__ shi, const uint64_t *__restrict__ klo, const uint32_t *__restrict__ val,
+                const float2 *__restrict__ pos, uint32_t n, uint32_t *__restrict__ head, TreeStats *__restrict__ st, uint64_t frame)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i > n) return;
+    uint32_t h = 0;
+    if (i < st->massive) {
+        h = 1;
+        if (i > 0 && shi[i] == shi[i - 1] && klo[val[i]] == klo[val[i - 1]]) {
+            h = 0;
+            const float2 a = pos[val[i]], b = pos[val[i - 1]];
+            if (!(a.x == b.x && a.y == b.y) && atomicMax(&st->fail, 2u) < 2u) {
+                st->overflow_kind = 2; st->overflow_frame = frame; st->overflow_needed = i;
+                atomicAdd((unsigned long long *)&st->overflow_steps, 1ull);
+            }
+        }
+    }
+    head[i] = h;
+}
+
+__global__ __launch_bounds__(256)
+void tree_points(const uint64_t *__restrict__ shi, const uint64_t *__restrict__ klo, const uint32_t *__restrict__ val,
+                 const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx, uint32_t n,
+                 uint64_t *__restrict__ uhi, uint64_t *__restrict__ ulo, uint32_t *__restrict__ ufirst, TreeStats *__restrict__ st)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { st->points = (uint32_t)uidx[n]; return; }
+    if (!head[i]) return;
+    const uint32_t u = (uint32_t)uidx[i];
+    uhi[u] = shi[i]; ulo[u] = klo[val[i]]; ufirst[u] = i;
+}
+
+struct TreeKeys { const uint64_t *hi, *lo; uint32_t U; };
+
+__device__ __forceinline__ int tree_L(const TreeKeys &k, uint32_t u)      // levels shared by points u and u + 1; -1 past the ends
+{
+    if (u + 1u >= k.U || u == 0xffffffffu) return -1;
+    return tree_lcp(k.hi[u], k.lo[u], k.hi[u + 1], k.lo[u + 1]);
+}
+
+__device__ __forceinline__ int tree_leaf_depth(const TreeKeys &k, uint32_t u)
+{
+    const int a = tree_L(k, u - 1u), b = tree_L(k, u);
+    return (a > b ? a : b) + 1;
+}
+
+// empty quadrants passed when the traversal leaves point u's cells from its leaf up to (and including) level `from`
+__device__ __forceinline__ uint32_t tree_closing(const TreeKeys &k, uint32_t u, int from, int leaf_depth)
+{
+    uint32_t c = 0;
+    const uint64_t hi = k.hi[u], lo = k.lo[u];
+    for (int l = leaf_depth; l >= from; --l) c += 3u - tree_digit(hi, lo, l - 1);
+    return c;
+}
+
+// cnt[u], u = 0 .. U: nodes point u writes (U: the closing run of the last point; the empty root when there is no point);
+// cnt[u] = 0 past U.  n + 2 entries.
+__global__ __launch_bounds__(256)
+void tree_count(const uint64_t *__restrict__ uhi, const uint64_t *__restrict__ ulo, uint32_t n, uint32_t *__restrict__ cnt,
+                TreeStats *__restrict__ st)
+{
+    const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+    if (u > n + 1u) return;
+    const TreeKeys k{uhi, ulo, st->points};
+    uint32_t c = 0;
+    if (st->fail) c = 0;
+    else if (u == k.U) c = k.U ? tree_closing(k, k.U - 1u, 1, tree_leaf_depth(k, k.U - 1u)) : 1u;
+    else if (u < k.U) {
+        const int lp = tree_L(k, u - 1u), d = tree_leaf_depth(k, u);
+        const uint64_t hi = uhi[u], lo = ulo[u];
+        if (u > 0) {
+            c += tree_closing(k, u - 1u, lp + 2, tree_leaf_depth(k, u - 1u));
+            c += tree_digit(hi, lo, lp) - tree_digit(uhi[u - 1], ulo[u - 1], lp) - 1u;
+        }
+        for (int l = lp + 1; l < d; ++l) c += 1u + tree_digit(hi, lo, l);
+        c += 1u;
+        if ((uint32_t)d > st->max_depth) atomicMax(&st->max_depth, (uint32_t)d);
+    }
+    cnt[u] = c;
+}
+
+// ---- nodes ----------------------------------------------------------------------------------------------------------
+constexpr uint8_t TREE_BRANCH = 0x80;
+
+__global__ __launch_bounds__(256)
+void tree_emit(const uint64_t *__restrict__ uhi, const uint64_t *__restrict__ ulo, const uint32_t *__restrict__ ufirst,
+               const uint32_t *__restrict__ val, const float2 *__restrict__ pos, const float *__restrict__ mass,
+               const uint64_t *__restrict__ base, uint32_t n, const TreeRoot *__restrict__ root, uint64_t cap,
+               float4 *__restrict__ nd, uint32_t *__restrict__ nx, uint8_t *__restrict__ dp, TreeStats *__restrict__ st, uint64_t frame)
+{
+#pragma clang fp contract(off)
+    const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+    if (st->fail == 2u) return;
+    const TreeKeys k{uhi, ulo, st->points};
+    const uint64_t total = base[n + 1u];                  // exclusive scan of n + 2 counts (64-bit sums): the last entry is the total
+    if (total > cap) {
+        if (u == 0) {
+            st->fail = 1; st->nodes = total; st->overflow_kind = 1; st->overflow_frame = frame; st->overflow_needed = total;
+            st->overflow_steps += 1;
+        }
+        return;
+    }
+    if (u > k.U) return;
+    if (u == 0) st->nodes = total;
+    uint32_t w = (uint32_t)base[u];                     // total <= cap < 2^32 from here on
+    // (w < total always: tree_count counted exactly these nodes; the bound keeps a disagreement inside the arrays)
+    auto put = [&](float4 rec, uint32_t next, uint8_t depth) { if (w < total) { nd[w] = rec; nx[w] = next; dp[w] = depth; } ++w; };
+    auto empty = [&](int depth) { put(make_float4(0.f, 0.f, 0.f, root->s2[depth]), w + 1u, (uint8_t)depth); };
+    if (u == k.U) {
+        if (k.U == 0) { empty(0); return; }
+        const uint64_t hi = uhi[u - 1], lo = ulo[u - 1];
+        for (int l = tree_leaf_depth(k, u - 1u); l >= 1; --l)
+            for (uint32_t q = tree_digit(hi, lo, l - 1) + 1u; q < 4u; ++q) empty(l);
+        return;
+    }
+    const int lp = tree_L(k, u - 1u), d = tree_leaf_depth(k, u);
+    const uint64_t hi = uhi[u], lo = ulo[u];
+    if (u > 0) {
+        const uint64_t phi = uhi[u - 1], plo = ulo[u - 1];
+        for (int l = tree_leaf_depth(k, u - 1u); l >= lp + 2; --l)
+            for (uint32_t q = tree_digit(phi, plo, l - 1) + 1u; q < 4u; ++q) empty(l);
+        for (uint32_t q = tree_digit(phi, plo, lp) + 1u; q < tree_digit(hi, lo, lp); ++q) empty(lp + 1);
+    }
+    for (int l = lp + 1; l < d; ++l) {
+        // the branch of depth l on u's path: u is its first point; its last one is the last point sharing l levels with u
+        uint32_t a = u + 1u, b = k.U - 1u;                // (a is inside: L(u) >= l because d > l)
+        while (a < b) {
+            const uint32_t mid = a + (b - a + 1u) / 2u;
+            if (tree_lcp(hi, lo, uhi[mid], ulo[mid]) >= l) a = mid; else b = mid - 1u;
+        }
+        put(make_float4(0.f, 0.f, 0.f, root->s2[l]), (uint32_t)base[a + 1u] + tree_closing(k, a, l + 1, tree_leaf_depth(k, a)), (uint8_t)l | TREE_BRANCH);
+        for (uint32_t q = 0; q < tree_digit(hi, lo, l); ++q) empty(l + 1);
+    }
+    // the leaf: the position its bodies share, their masses added in ascending body index (Quadtree.hpp:56-60)
+    const uint32_t f = ufirst[u], e = u + 1u < k.U ? ufirst[u + 1u] : st->massive;
+    const float2 p = pos[val[f]];
+    float m = mass[val[f]];
+    for (uint32_t j = f + 1u; j < e; ++j) m = m + mass[val[j]];
+    put(make_float4(p.x, p.y, m, root->s2[d]), w + 1u, (uint8_t)d);
+}
+
+// Centres of mass of the branches of depth `level` (launched for level = TREE_DEPTH_CAP - 1 ... 0): Quadtree.hpp:236-258.
+__global__ __launch_bounds__(256)
+void tree_com(float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint8_t *__restrict__ dp, uint32_t level,
+              const TreeStats *__restrict__ st)
+{
+#pragma clang fp contract(off)
+    if (st->fail || level >= st->max_depth) return;
+    const uint32_t total = (uint32_t)st->nodes;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        if (dp[i] != ((uint8_t)level | TREE_BRANCH)) continue;
+        float sx = 0.f, sy = 0.f, sm = 0.f;
+        uint32_t c = i + 1u;
+        for (int q = 0; q < 4 && c < total; ++q) {
+            const float4 ch = nd[c];
+            sx = sx + ch.x * ch.z;
+            sy = sy + ch.y * ch.z;
+            sm = sm + ch.z;
+            c = nx[c];
+        }
+        if (sm > 0.f) {
+            const float inv = 1.0f / sm;                  // Vec2::operator/=, Vec2.hpp:159-165
+            sx = sx * inv; sy = sy * inv;
+        }
+        nd[i] = make_float4(sx, sy, sm, nd[i].w);
+    }
+}
+
+// ---- walk -----------------------------------------------------------------------------------------------------------
+// Quadtree::acc (Quadtree.hpp:113-155), one lane per body, bodies in key order.  The nodes are in pre-order: an accepted
+// node is left through `next`, any other through index + 1 (a leaf's next IS index + 1, and a leaf adds nothing: the
+// reference's leaf ranges are empty).  RSQ_QUAKE: one running sum in visit order, no contraction — the reference's bits.
+// RSQ_EXACT: the same acceptance test, the term with v_rsq_f32 and FMA.
+template <int RSQ>
+__global__ __launch_bounds__(256)
+void tree_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
+               const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
+               const TreeStats *__restrict__ st)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || st->fail) return;
+    const uint32_t b = val[i];
+    const float2 p = pos[b];
+    const uint32_t total = (uint32_t)st->nodes;
+    float sx = 0.f, sy = 0.f;
+    uint32_t node = 0;
+    while (node < total) {
+        const float4 q = nd[node];
+        float dx, dy, d2;
+        bool far;
+        {
+#pragma clang fp contract(off)
+            dx = q.x - p.x; dy = q.y - p.y;
+            d2 = dx * dx + dy * dy;
+            far = q.w < d2 * theta2;
+        }
+        if (far) {
+            if (d2 > 0.f) {
+                if constexpr (RSQ == RSQ_QUAKE) {
+#pragma clang fp contract(off)
+                    const float inv = quake_rsqrt(d2 + eps2);
+                    const float inv3 = inv * inv * inv;
+                    const float s = q.z * inv3;
+                    sx = sx + dx * s;
+                    sy = sy + dy * s;
+                } else {
+                    const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
+                    const float s = q.z * (inv * inv * inv);
+                    sx = __builtin_fmaf(dx, s, sx);
+                    sy = __builtin_fmaf(dy, s, sy);
+                }
+            }
+            const uint32_t next = nx[node];
+            node = next > node ? next : node + 1u;           // (next > node always; the walk ends whatever the array holds)
+        } else {
+            node = node + 1u;
+        }
+    }
+    acc[b] = make_float2(sx, sy);
+}
+
+// Kick and drift with acc[] as written by tree_walk.  A failed build integrates nothing: the positions are carried over.
+template <typename L, bool STRICT>
+__global__ __launch_bounds__(256)
+void tree_integrate(const float2 *__restrict__ pos_cur, float2 *__restrict__ pos_next, float2 *__restrict__ vel, float2 *__restrict__ acc,
+                    uint32_t n, float dt_kick, float dt_drift, int extras, int flags, const TreeStats *__restrict__ st)
+{
+    const uint32_t li = blockIdx.x * 256u + threadIdx.x;
+    if (li >= n) return;
+    if (st->fail) {
+        if (flags & INTEG_DRIFT) pos_next[li] = pos_cur[li];
+        return;
+    }
+    kick_drift_one<L, STRICT>(acc[li], li, pos_cur, pos_next, vel, acc, 0u, dt_kick, dt_drift, extras, flags);
+}
+
+} // namespace nbk

@@ -23,6 +23,8 @@
 // from `Simulation()` follows the reference's gravity + clamp + boundary, not its collisions.  Built with
 // -DNBODY_COLLIDE=1, reference_params() adds NB_EXTRA_COLLIDE and step() ends with the library's restatement of
 // collide() (the pair order and the once-per-pair rule differ from the reference's spatial hash).
+// Built with -DNBODY_TREE=1, the force is the reference's own Barnes-Hut walk (NB_FORCE_TREE, theta = 1, Quake rsqrt): the
+// reference's accelerations bit for bit.  `quadtree.nodes` is not filled (the GUI's tree overlay stays empty).
 #pragma once
 #include <atomic>
 #include <cmath>
@@ -187,6 +189,10 @@ private:
         p.extras = NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY;     // Simulation.hpp:133-155
 #if defined(NBODY_COLLIDE) && NBODY_COLLIDE
         p.extras |= NB_EXTRA_COLLIDE;                       // Simulation.hpp:72,216-346
+#endif
+#if defined(NBODY_TREE) && NBODY_TREE
+        p.force = NB_FORCE_TREE;                            // Simulation.hpp:176-214: Barnes-Hut, theta = 1 (:59), the reference's
+        p.rsqrt_mode = NB_RSQRT_QUAKE;                      // own arithmetic (Quadtree.hpp:106-111): its frames bit for bit
 #endif
         return &p;
     }

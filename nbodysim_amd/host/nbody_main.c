@@ -9,6 +9,7 @@
  *              [-sequential] [-kdk] [-dump FILE] [-load FILE] [-sync-every K]
  *              [-reference-ics]  the reference's own start: Simulation()'s 25 000-body disc (or -n N of it),
  *                            eps = 1, dt = 0.01, velocity clamp + soft boundary (Simulation.hpp:58-65,116-163)
+ *              [-tree [theta]]  the reference's Barnes-Hut force (NB_FORCE_TREE; theta defaults to 1, Simulation.hpp:59)
  *              [-collide]    end every step with the reference's hard-sphere collisions (NB_EXTRA_COLLIDE, Simulation.hpp:216-346)
  *              [-shards P]   P sharded handles driven from this one process (device r mod #GPUs),
  *                            exchanged with nb_exchange_positions: multi-GPU without RCCL
@@ -93,6 +94,10 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-sequential")) p.sum_order = NB_SUM_SEQUENTIAL;
         else if (!strcmp(argv[i], "-kdk")) p.integrator = NB_INTEGRATOR_KDK;
         else if (!strcmp(argv[i], "-collide")) p.extras |= NB_EXTRA_COLLIDE;
+        else if (!strcmp(argv[i], "-tree")) {
+            p.force = NB_FORCE_TREE;
+            if (i + 1 < argc && argv[i + 1][0] != '-') p.theta = (float)atof(argv[++i]);
+        }
         else if (!strcmp(argv[i], "-dump") && i + 1 < argc) dump = argv[++i];
         else if (!strcmp(argv[i], "-load") && i + 1 < argc) {
             /* the header's parameters become the defaults of this run; later options override them */

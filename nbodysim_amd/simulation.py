@@ -68,6 +68,8 @@ class Simulation:
         pos_rows: int = 0,
         static_items: bool = False,
         collide: bool = False,
+        force: str = "direct",
+        theta: float = 1.0,
         library=None,
     ):
         """The last arguments (from ``uniform_mass`` on) are ``nb_params.flags`` and the launch-geometry tuning fields
@@ -75,7 +77,8 @@ class Simulation:
         (default) = both per-pair mass multiplies, True = fold the masses into the pair geometry wherever representable
         (include/nbody.h, NB_FLAG_MASS_SCALING), "measured" = the library measures at upload whether folding is harmless for
         these bodies and folds only then (NB_FLAG_MASS_SCALING_MEASURED).  ``collide``: end every step with the reference's
-        hard-sphere collisions (adds NB_EXTRA_COLLIDE to ``extras``; unsharded 2-D kick-drift only).  ``library``: another
+        hard-sphere collisions (adds NB_EXTRA_COLLIDE to ``extras``; unsharded 2-D kick-drift only).  ``force``: "direct" (every pair) or "tree" (the reference's
+        Barnes-Hut quadtree with opening parameter ``theta``, NB_FORCE_TREE; unsharded 2-D fp32 kick-drift only).  ``library``: another
         build of the library bound with ``_lib.bind`` (the tests' -DNB_TEST_HOOKS build); default the product."""
         lib = library if library is not None else L.load()
         if bodies.dtype not in (L.BODY_DTYPE, L.BODY3_DTYPE):
@@ -114,6 +117,8 @@ class Simulation:
         p.sym_chunk_pairs = sym_chunk_pairs
         p.sym_tile = sym_tile
         p.pos_rows = pos_rows
+        p.force = {"direct": L.NB_FORCE_DIRECT, "tree": L.NB_FORCE_TREE}[force]
+        p.theta = theta
         p.shard_rank, p.shard_world = shard_rank, shard_world
         if acc_buffers is not None:
             p.acc_buffers[0], p.acc_buffers[1] = acc_buffers
@@ -201,6 +206,14 @@ class Simulation:
     def collide_capacity(self, max_pairs: int) -> None:
         """Set the pair capacity of the collision path (``nb_collide_capacity``)."""
         L.check("nb_collide_capacity", self._lib.nb_collide_capacity(self._h, max_pairs), self._lib)
+
+    def tree_stats(self) -> dict:
+        """Figures of the last Barnes-Hut force evaluation (``nb_tree_stats``; synchronises): nodes, deepest leaf, evaluations
+        that failed (node capacity, depth cap) since creation."""
+        nodes, ovf = C.c_uint64(), C.c_uint64()
+        depth = C.c_uint32()
+        L.check("nb_tree_stats", self._lib.nb_tree_stats(self._h, C.byref(nodes), C.byref(depth), C.byref(ovf)), self._lib)
+        return {"nodes": int(nodes.value), "max_depth": int(depth.value), "overflow_steps": int(ovf.value)}
 
     def dump(self, path: str) -> None:
         L.check("nb_dump", self._lib.nb_dump(self._h, str(path).encode()), self._lib)
