@@ -173,10 +173,28 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          resident wave draws the next item of the list when it starts, so that the XCDs of a part, which are not
                                          equally fast, end together: -1.4 ... -2.3 % per step from 65 536 bodies up, same bits); this bit keeps
                                          item = workgroup index (A/B runs) */
-       NB_FLAG_SHARD_SINGLE    = 16 };/* shard_world = 1, i_count = n: run the sharded symmetric protocol (or, with
+       NB_FLAG_SHARD_SINGLE    = 16,  /* shard_world = 1, i_count = n: run the sharded symmetric protocol (or, with
                                          NB_FLAG_SHARD_ALLREDUCE, the replicated one) with ONE rank — every pair is "local",
                                          the reduce-scatter / all-gather degenerate to copies.  For rehearsing the exchange
                                          path (nb_comm_*, nb_exchange_*) on a single GPU; never faster than a plain handle */
+       /* 2048 is unassigned: nb_create rejects it like any unknown bit */
+       NB_FLAG_TREE_LEAVES     = 4096 };/* NB_FORCE_TREE only (with NB_FORCE_DIRECT nb_create returns NB_EINVAL, naming the combination):
+                                         the CONVERGENT Barnes-Hut force.  Cells, centres of mass, node order and the acceptance test
+                                         size^2 < d^2 * theta^2 are those of NB_FORCE_TREE without the bit; a leaf that is not accepted adds
+                                         its own term d * (mass * inv^3) when d^2 > 0 (its record is exact: one position, the summed mass).
+                                         Every inserted body is then counted exactly once per walker, inside an accepted cell or as its own
+                                         leaf, and the result converges to the direct sum as theta -> 0: theta = 0 IS the softened direct
+                                         sum over the distinct positions (a body's own leaf and the bodies coincident with it have d^2 = 0
+                                         and add nothing, as in the direct sum).  THIS IS NOT THE REFERENCE'S ARITHMETIC: the reference's
+                                         leaves add nothing, so every body there loses its nearest neighbours' pull and theta = 0 gives
+                                         zero; without the bit that behaviour is kept bit for bit.  With NB_RSQRT_QUAKE every body walks on
+                                         its own, one running sum in visit order (tests/tree_leaves_model.py restates it bit for bit).  With
+                                         NB_RSQRT_EXACT the walk the measurements chose runs (nb_describe: walk=lane, or walk=group where the
+                                         64 bodies of a wave walk together and a cell is accepted when all of them accept it: never coarser
+                                         than a body's own walk; massless bodies and bodies on a position that first appears in an earlier
+                                         window walk on their own).  Deterministic either way: two handles agree bit for bit, and permuting
+                                         the bodies permutes the bits.  nb_describe appends " leaves=1 walk=lane|group".
+                                         Everything the handle refuses or ignores as a tree handle it refuses or ignores with the bit too */
 
 /* ---- parameters ----------------------------------------------------------- */
 typedef struct nb_params {

@@ -172,6 +172,7 @@ struct nb_sim {
     // Barnes-Hut force (NB_FORCE_TREE, nb_tree.hip.h): nothing below is allocated for a direct-sum handle
     bool tree = false;
     float tree_theta2 = 1.0f;                  // theta * theta, Quadtree.hpp:18
+    bool tree_leaves = false;                  // NB_FLAG_TREE_LEAVES: leaves that are not accepted contribute
     uint64_t tree_cap = 0;                     // node capacity: nodes allocated
     uint64_t tree_ovf_reported = 0;            // failed evaluations already reported by a synchronising call
     uint64_t *tree_k64[4] = {nullptr, nullptr, nullptr, nullptr};   // key words by body: high, low; two sort buffers
@@ -963,6 +964,10 @@ static int tree_alloc(nb_sim *s)
     return NB_OK;
 }
 
+// The walk of a NB_FLAG_TREE_LEAVES handle: the wave-uniform one with the hardware rsqrt, the per-lane one (the form the CPU
+// model restates bit for bit) with the Quake rsqrt.
+static bool tree_walk_is_group(const nb_sim *s) { return s->tree_leaves && s->p.rsqrt_mode != NB_RSQRT_QUAKE; }
+
 // One force evaluation at pos[cur] into acc[] (nb_tree.hip.h has the pipeline).  The walk is "the force kernel" of nb_profile_read.
 static int launch_tree_force(nb_sim *s)
 {
@@ -996,9 +1001,17 @@ static int launch_tree_force(nb_sim *s)
     std::pair<hipEvent_t, hipEvent_t> pr;
     if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
     const float eps2 = s->p.eps * s->p.eps;
-    with_flags([&](auto q) {
-        tree_walk<q ? RSQ_QUAKE : RSQ_EXACT><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st);
-    }, s->p.rsqrt_mode == NB_RSQRT_QUAKE);
+    if (tree_walk_is_group(s)) {     // the group walk, then the few lanes that left it (nb_tree.hip.h): one "force kernel" interval
+        tree_walk_group<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
+                                                  s->tree_head, s->tree_uidx, s->tree_ufirst);
+        tree_walk_alone<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
+                                                  s->tree_head, s->tree_uidx, s->tree_ufirst);
+    } else {
+        with_flags([&](auto q, auto leaves) {
+            tree_walk<q ? RSQ_QUAKE : RSQ_EXACT, leaves><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2,
+                                                                                     (float2 *)s->acc, st);
+        }, s->p.rsqrt_mode == NB_RSQRT_QUAKE, s->tree_leaves);
+    }
     HIPCHK(hipGetLastError());
     if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
     return NB_OK;
@@ -1133,7 +1146,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
         nb_set_error("nb_create: quake rsqrt / sequential order are fp32 (reference arithmetic) modes");
         return nullptr;
     }
-    if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
+    if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED | NB_FLAG_TREE_LEAVES)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
     if (p.extras & ~(NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY | NB_EXTRA_COLLIDE)) { nb_set_error("nb_create: unknown bits in extras 0x%x", (unsigned)p.extras); return nullptr; }
     if (p.extras & NB_EXTRA_COLLIDE) {
         const char *why = p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
@@ -1145,6 +1158,10 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     }
     if (p.force != NB_FORCE_DIRECT && p.force != NB_FORCE_TREE) { nb_set_error("nb_create: bad force %d", p.force); return nullptr; }
     if (!(p.theta >= 0.0f) || !std::isfinite(p.theta)) { nb_set_error("nb_create: theta must be >= 0 and finite"); return nullptr; }
+    if ((p.flags & NB_FLAG_TREE_LEAVES) && p.force != NB_FORCE_TREE) {
+        nb_set_error("nb_create: NB_FLAG_TREE_LEAVES with NB_FORCE_DIRECT: the flag selects a walk of the Barnes-Hut force (NB_FORCE_TREE)");
+        return nullptr;
+    }
     if (p.force == NB_FORCE_TREE) {
         const char *why = p.precision == NB_FP64 ? "NB_FP64" : p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
                         : p.shard_world > 1 ? "shard_world > 1" : (p.i_count != 0 && p.i_count < n) ? "i_count < n"
@@ -1229,6 +1246,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     s->slabs_cap = s->slabs_all > s->slabs_two_phase ? s->slabs_all : s->slabs_two_phase;
     s->tree = p.force == NB_FORCE_TREE;
     s->tree_theta2 = p.theta * p.theta;
+    s->tree_leaves = s->tree && (p.flags & NB_FLAG_TREE_LEAVES) != 0;
     if ((e = hipMalloc(&s->mass, n * s->rsz)) != hipSuccess) return fail("hipMalloc mass", e);
     if ((e = hipMalloc((void **)&s->radius, n * sizeof(float))) != hipSuccess) return fail("hipMalloc radius", e);
     if ((e = hipMalloc(&s->vel, s->i_count * r2)) != hipSuccess) return fail("hipMalloc vel", e);
@@ -2240,8 +2258,9 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
                  s->coll_large_n, (unsigned long long)s->coll_cap, resolve);
     const size_t len = strlen(buf);
     if (len < buflen) {
-        if (s->tree) snprintf(buf + len, buflen - len, " | force=tree theta=%.6g node_capacity=%llu depth_cap=%d", (double)s->p.theta,
-                              (unsigned long long)s->tree_cap, TREE_DEPTH_CAP);
+        if (s->tree) snprintf(buf + len, buflen - len, " | force=tree theta=%.6g node_capacity=%llu depth_cap=%d%s", (double)s->p.theta,
+                              (unsigned long long)s->tree_cap, TREE_DEPTH_CAP,
+                              !s->tree_leaves ? "" : tree_walk_is_group(s) ? " leaves=1 walk=group" : " leaves=1 walk=lane");
         else snprintf(buf + len, buflen - len, " | force=direct");
     }
     return NB_OK;

@@ -334,14 +334,14 @@ void tree_com(float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const ui
 // node is left through `next`, any other through index + 1 (a leaf's next IS index + 1, and a leaf adds nothing: the
 // reference's leaf ranges are empty).  RSQ_QUAKE: one running sum in visit order, no contraction — the reference's bits.
 // RSQ_EXACT: the same acceptance test, the term with v_rsq_f32 and FMA.
-template <int RSQ>
-__global__ __launch_bounds__(256)
-void tree_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
-               const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
-               const TreeStats *__restrict__ st)
+// LEAVES (NB_FLAG_TREE_LEAVES): a leaf that is not accepted adds its own term (its record is exact: one position, the summed
+// mass), so every inserted body is counted once, in an accepted cell or as its leaf, and theta -> 0 is the direct sum.  The
+// nodes visited are the same; an empty quadrant (mass 0) adds nothing and costs no rsqrt.
+template <int RSQ, bool LEAVES>
+__device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restrict__ nd, const uint32_t *__restrict__ nx,
+                                              const uint32_t *__restrict__ val, const float2 *__restrict__ pos, float eps2, float theta2,
+                                              float2 *__restrict__ acc, const TreeStats *__restrict__ st)
 {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n || st->fail) return;
     const uint32_t b = val[i];
     const float2 p = pos[b];
     const uint32_t total = (uint32_t)st->nodes;
@@ -357,27 +357,111 @@ void tree_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, c
             d2 = dx * dx + dy * dy;
             far = q.w < d2 * theta2;
         }
-        if (far) {
-            if (d2 > 0.f) {
-                if constexpr (RSQ == RSQ_QUAKE) {
+        auto term = [&]() {
+            if constexpr (RSQ == RSQ_QUAKE) {
 #pragma clang fp contract(off)
-                    const float inv = quake_rsqrt(d2 + eps2);
-                    const float inv3 = inv * inv * inv;
-                    const float s = q.z * inv3;
-                    sx = sx + dx * s;
-                    sy = sy + dy * s;
-                } else {
-                    const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
-                    const float s = q.z * (inv * inv * inv);
-                    sx = __builtin_fmaf(dx, s, sx);
-                    sy = __builtin_fmaf(dy, s, sy);
-                }
+                const float inv = quake_rsqrt(d2 + eps2);
+                const float inv3 = inv * inv * inv;
+                const float s = q.z * inv3;
+                sx = sx + dx * s;
+                sy = sy + dy * s;
+            } else {
+                const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
+                const float s = q.z * (inv * inv * inv);
+                sx = __builtin_fmaf(dx, s, sx);
+                sy = __builtin_fmaf(dy, s, sy);
             }
+        };
+        if (far) {
+            if (d2 > 0.f) term();
             const uint32_t next = nx[node];
             node = next > node ? next : node + 1u;           // (next > node always; the walk ends whatever the array holds)
         } else {
+            if constexpr (LEAVES) {
+                if (q.z != 0.f && d2 > 0.f && nx[node] == node + 1u) term();
+            }
             node = node + 1u;
         }
+    }
+    acc[b] = make_float2(sx, sy);
+}
+
+template <int RSQ, bool LEAVES>
+__global__ __launch_bounds__(256)
+void tree_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
+               const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
+               const TreeStats *__restrict__ st)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || st->fail) return;
+    tree_walk_one<RSQ, LEAVES>(i, nd, nx, val, pos, eps2, theta2, acc, st);
+}
+
+// The wave-uniform walk of NB_FLAG_TREE_LEAVES with NB_RSQRT_EXACT: one wave is one group, the 64 bodies at sorted positions
+// [64 w, 64 w + 64) of `val`; a workgroup is four independent groups (no LDS, no barrier).  The node index is the same in every
+// lane (formed through readfirstlane, so that the record and `next` are loaded once per wave); every lane evaluates its own
+// acceptance test with the arithmetic of tree_walk, and a cell is accepted when ALL lanes of the group accept it (lanes that
+// have left do not vote).  Every lane therefore opens at least what its own walk opens, there is no divergence in the loop,
+// and every inserted body is still counted once per lane.
+// A body's result depends on the positions in its group, so a group must not depend on the order of the bodies.  Two kinds
+// of lane would make it: massless bodies (they sort last, by index alone) and a body on a position that first appears in an
+// earlier group (which of the bodies sharing the position falls behind the boundary follows the index).  These lanes leave
+// the group walk (tree_lane_alone) and tree_walk_alone gives each of them its own per-lane walk afterwards.
+__device__ __forceinline__ bool tree_lane_alone(uint32_t i, const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
+                                                const uint32_t *__restrict__ ufirst, const TreeStats *__restrict__ st)
+{
+    if (i >= st->massive) return true;
+    if (head[i]) return false;
+    return (ufirst[(uint32_t)uidx[i] - 1u] >> 6) != (i >> 6);        // (not a head: at least one key starts before i)
+}
+
+__global__ __launch_bounds__(256)
+void tree_walk_alone(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
+                     const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
+                     const TreeStats *__restrict__ st, const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
+                     const uint32_t *__restrict__ ufirst)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || st->fail || !tree_lane_alone(i, head, uidx, ufirst, st)) return;
+    tree_walk_one<RSQ_EXACT, true>(i, nd, nx, val, pos, eps2, theta2, acc, st);
+}
+
+__global__ __launch_bounds__(256)
+void tree_walk_group(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
+                     const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
+                     const TreeStats *__restrict__ st, const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
+                     const uint32_t *__restrict__ ufirst)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || st->fail || tree_lane_alone(i, head, uidx, ufirst, st)) return;
+    const uint32_t b = val[i];
+    const float2 p = pos[b];
+    const uint32_t total = (uint32_t)st->nodes;
+    float sx = 0.f, sy = 0.f;
+    uint32_t node = 0;
+    while (node < total) {
+        node = (uint32_t)__builtin_amdgcn_readfirstlane((int)node);
+        const float4 q = nd[node];
+        const uint32_t next = nx[node];
+        float dx, dy, d2;
+        bool far;
+        {
+#pragma clang fp contract(off)
+            dx = q.x - p.x; dy = q.y - p.y;
+            d2 = dx * dx + dy * dy;
+            far = q.w < d2 * theta2;
+        }
+        const bool all_far = __ballot(!far) == 0ull;
+        const bool leaf = next == node + 1u;
+        if (all_far || (leaf && q.z != 0.f)) {
+            if (d2 > 0.f) {
+                const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
+                const float s = q.z * (inv * inv * inv);
+                sx = __builtin_fmaf(dx, s, sx);
+                sy = __builtin_fmaf(dy, s, sy);
+            }
+        }
+        node = all_far && next > node ? next : node + 1u;    // (a leaf's next is node + 1)
     }
     acc[b] = make_float2(sx, sy);
 }

@@ -10,6 +10,8 @@
  *              [-reference-ics]  the reference's own start: Simulation()'s 25 000-body disc (or -n N of it),
  *                            eps = 1, dt = 0.01, velocity clamp + soft boundary (Simulation.hpp:58-65,116-163)
  *              [-tree [theta]]  the reference's Barnes-Hut force (NB_FORCE_TREE; theta defaults to 1, Simulation.hpp:59)
+ *              [-leaves]     with -tree: the convergent tree force (NB_FLAG_TREE_LEAVES): leaves that are not accepted contribute,
+ *                            so the result tends to the direct sum as theta -> 0; not the reference's arithmetic
  *              [-collide]    end every step with the reference's hard-sphere collisions (NB_EXTRA_COLLIDE, Simulation.hpp:216-346)
  *              [-shards P]   P sharded handles driven from this one process (device r mod #GPUs),
  *                            exchanged with nb_exchange_positions: multi-GPU without RCCL
@@ -98,6 +100,7 @@ int main(int argc, char **argv)
             p.force = NB_FORCE_TREE;
             if (i + 1 < argc && argv[i + 1][0] != '-') p.theta = (float)atof(argv[++i]);
         }
+        else if (!strcmp(argv[i], "-leaves")) p.flags |= NB_FLAG_TREE_LEAVES;
         else if (!strcmp(argv[i], "-dump") && i + 1 < argc) dump = argv[++i];
         else if (!strcmp(argv[i], "-load") && i + 1 < argc) {
             /* the header's parameters become the defaults of this run; later options override them */

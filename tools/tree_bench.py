@@ -9,6 +9,14 @@ two waits.  Prints one JSON line per case: milliseconds per step, the walk's sha
 last build, and direct / tree.
 
     rocprofv3 --kernel-trace --stats -- python tools/tree_bench.py --trace CASE      50 tree steps alone: microseconds per kernel
+
+    python tools/tree_bench.py --theta T [--leaves] [case ...]      the walk alone, hardware rsqrt, opening parameter T, with
+                                               --leaves the convergent force (NB_FLAG_TREE_LEAVES); cases 262144 and 1048576 by default
+
+With --theta the handle steps for at least 2 s, then FIVE stretches are timed; per stretch the milliseconds per step (host clock
+between two waits) and the milliseconds per walk (nb_profile_read, device events around the walk).  One JSON line per case: the
+five figures of each, their median and spread (max - min), and the walk nb_describe names.  A library built from another commit
+is measured through NBODY_HIP_LIB (the cases without --leaves need nothing this tool adds).
 """
 from __future__ import annotations
 
@@ -21,7 +29,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import nbodysim_amd as nb  # noqa: E402
 
 
-def settled_ms(sim, dt: float, warm_s: float = 2.0, timed_s: float = 1.0) -> float:
+def settle(sim, dt: float, warm_s: float = 2.0) -> float:
+    """Step for at least warm_s seconds; returns the seconds one step takes."""
     sim.advance(2, dt)
     sim.wait()
     t0 = time.perf_counter()
@@ -34,11 +43,44 @@ def settled_ms(sim, dt: float, warm_s: float = 2.0, timed_s: float = 1.0) -> flo
         sim.advance(k, dt)
         sim.wait()
         left -= k * est
+    return est
+
+
+def settled_ms(sim, dt: float, warm_s: float = 2.0, timed_s: float = 1.0) -> float:
+    est = settle(sim, dt, warm_s)
     k = max(3, min(int(timed_s / est), 5000))
     t0 = time.perf_counter()
     sim.advance(k, dt)
     sim.wait()
     return (time.perf_counter() - t0) / k * 1e3
+
+
+def run_walk(case: str, theta: float, leaves: bool, stretches: int = 5, timed_s: float = 1.0) -> dict:
+    bodies, dt = nb.plummer_2d(int(case), 42), 1e-3
+    kw = dict(tree_leaves=True) if leaves else {}
+    with nb.Simulation(bodies, force="tree", rsqrt="exact", theta=theta, eps=0.01, device=0, **kw) as sim:
+        d = sim.describe()
+        out = {"case": case, "n": int(bodies.shape[0]), "theta": theta, "leaves": int(leaves),
+               "walk": d.split(" walk=")[1].split()[0] if " walk=" in d else "lane"}
+        est = settle(sim, dt)
+        k = max(3, min(int(timed_s / est), 5000))
+        step_ms, walk_ms = [], []
+        sim.profile(True)
+        sim.profile_read()
+        for _ in range(stretches):
+            t0 = time.perf_counter()
+            sim.advance(k, dt)
+            sim.wait()
+            step_ms.append((time.perf_counter() - t0) / k * 1e3)
+            ms, launches = sim.profile_read()
+            walk_ms.append(ms / launches)
+        out["steps_per_stretch"] = k
+        for name, v in (("walk_ms", walk_ms), ("step_ms", step_ms)):
+            out[name] = [round(a, 4) for a in v]
+            out[name + "_median"] = round(sorted(v)[len(v) // 2], 4)
+            out[name + "_spread"] = round(max(v) - min(v), 4)
+        out.update(sim.tree_stats())
+    return out
 
 
 def run(case: str) -> dict:
@@ -81,6 +123,16 @@ def trace(case: str, steps: int = 50) -> None:
 if __name__ == "__main__":
     if sys.argv[1:2] == ["--trace"]:
         trace(sys.argv[2])
+        sys.exit(0)
+    if "--theta" in sys.argv:
+        args = sys.argv[1:]
+        theta = float(args.pop(args.index("--theta") + 1))
+        args.remove("--theta")
+        leaves = "--leaves" in args
+        if leaves:
+            args.remove("--leaves")
+        for c in args or ["262144", "1048576"]:
+            print(json.dumps(run_walk(c, theta, leaves)), flush=True)
         sys.exit(0)
     for c in sys.argv[1:] or ["default", "262144", "1048576", "8388608"]:
         print(json.dumps(run(c)), flush=True)
