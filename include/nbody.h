@@ -177,8 +177,8 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          NB_FLAG_SHARD_ALLREDUCE, the replicated one) with ONE rank — every pair is "local",
                                          the reduce-scatter / all-gather degenerate to copies.  For rehearsing the exchange
                                          path (nb_comm_*, nb_exchange_*) on a single GPU; never faster than a plain handle */
-       /* 2048 is unassigned: nb_create rejects it like any unknown bit */
-       NB_FLAG_TREE_LEAVES     = 4096 };/* NB_FORCE_TREE only (with NB_FORCE_DIRECT nb_create returns NB_EINVAL, naming the combination):
+       /* 2048 is unassigned (4096 and 8192 are the two tree bits below): nb_create rejects it like any unknown bit */
+       NB_FLAG_TREE_LEAVES     = 4096,  /* NB_FORCE_TREE only (with NB_FORCE_DIRECT nb_create returns NB_EINVAL, naming the combination):
                                          the CONVERGENT Barnes-Hut force.  Cells, centres of mass, node order and the acceptance test
                                          size^2 < d^2 * theta^2 are those of NB_FORCE_TREE without the bit; a leaf that is not accepted adds
                                          its own term d * (mass * inv^3) when d^2 > 0 (its record is exact: one position, the summed mass).
@@ -195,6 +195,27 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          window walk on their own).  Deterministic either way: two handles agree bit for bit, and permuting
                                          the bodies permutes the bits.  nb_describe appends " leaves=1 walk=lane|group".
                                          Everything the handle refuses or ignores as a tree handle it refuses or ignores with the bit too */
+       NB_FLAG_TREE_QUADRUPOLE = 8192 };/* NB_FORCE_TREE with NB_FLAG_TREE_LEAVES only (alone, with NB_FORCE_DIRECT or without
+                                         NB_FLAG_TREE_LEAVES nb_create returns NB_EINVAL, naming the flag and the missing partner): accepted
+                                         cells carry the next multipole term.  Every branch keeps, beside its centre of mass c, the raw second
+                                         moment M = sum m_k (y_k - c)(y_k - c)^T over the inserted positions of its subtree (xx, xy, yy; raw,
+                                         not traceless, because the kernel is softened), computed bottom-up in the centre-of-mass pass from
+                                         the children's moments in quadrant order 0..3 (parallel-axis form, fp32, no contraction).  The nodes
+                                         visited, the acceptance test, the group vote and the "walks alone" rule are those of
+                                         NB_FLAG_TREE_LEAVES; only the term of an accepted BRANCH changes: with d = c - body position,
+                                         R^2 = d^2 + eps^2 and m its mass it adds
+                                             d * (m R^-3 + 7.5 (d^T M d) R^-7 - 1.5 tr(M) R^-5) - 3 (M d) R^-5
+                                         (the dipole vanishes about c; with eps = 0 the textbook quadrupole, Q = 3 M - tr(M) I).  A leaf has
+                                         M = 0: its term, accepted or not, is the monopole term, instruction for instruction.  theta = 0
+                                         never accepts a cell, so the result is that of the NB_FLAG_TREE_LEAVES handle bit for bit.  With
+                                         NB_RSQRT_QUAKE the per-lane walk runs with one running sum and no contraction
+                                         (tests/tree_quad_model.py restates it bit for bit); with NB_RSQRT_EXACT the walk nb_describe names,
+                                         where the moment record of a cell the whole wave accepts arrives once per wave.  Deterministic as
+                                         before: two handles agree bit for bit, permuting the bodies permutes the bits.  Memory: one 16-byte
+                                         record per node in an array of its own, 16 B x (16 n + 4096) = +256 B per body on top of the 535 B
+                                         per body of a tree handle, allocated only with the bit.  nb_describe appends " quad=1" after
+                                         "walk=...".  Without the bit nothing changes: same bits, same launches, same memory.  Everything a
+                                         NB_FLAG_TREE_LEAVES handle refuses or ignores it refuses or ignores with the bit too */
 
 /* ---- parameters ----------------------------------------------------------- */
 typedef struct nb_params {

@@ -173,6 +173,7 @@ struct nb_sim {
     bool tree = false;
     float tree_theta2 = 1.0f;                  // theta * theta, Quadtree.hpp:18
     bool tree_leaves = false;                  // NB_FLAG_TREE_LEAVES: leaves that are not accepted contribute
+    bool tree_quad = false;                    // NB_FLAG_TREE_QUADRUPOLE: accepted branches add their second moment
     uint64_t tree_cap = 0;                     // node capacity: nodes allocated
     uint64_t tree_ovf_reported = 0;            // failed evaluations already reported by a synchronising call
     uint64_t *tree_k64[4] = {nullptr, nullptr, nullptr, nullptr};   // key words by body: high, low; two sort buffers
@@ -188,6 +189,7 @@ struct nb_sim {
     float4 *tree_nd = nullptr;                 // node records {com.x, com.y, mass, size^2}
     uint32_t *tree_nx = nullptr;               // next: index + subtree size
     uint8_t *tree_dp = nullptr;                // depth | TREE_BRANCH
+    float4 *tree_qm = nullptr;                 // second moments {xx, xy, yy, 0} per node: NB_FLAG_TREE_QUADRUPOLE handles only
     void *tree_tmp = nullptr;                  // rocprim temporary storage (sort, scan)
     size_t tree_tmp_bytes = 0;
     TreeStats *tree_stats = nullptr;           // device
@@ -689,7 +691,8 @@ static void free_all(nb_sim *s)
     for (void *q : {(void *)s->tree_k64[0], (void *)s->tree_k64[1], (void *)s->tree_k64[2], (void *)s->tree_k64[3], (void *)s->tree_v32[0],
                     (void *)s->tree_v32[1], (void *)s->tree_v32[2], (void *)s->tree_head, (void *)s->tree_uidx, (void *)s->tree_uhi,
                     (void *)s->tree_ulo, (void *)s->tree_ufirst, (void *)s->tree_cnt, (void *)s->tree_base, (void *)s->tree_part,
-                    (void *)s->tree_root_dev, (void *)s->tree_nd, (void *)s->tree_nx, (void *)s->tree_dp, s->tree_tmp, (void *)s->tree_stats})
+                    (void *)s->tree_root_dev, (void *)s->tree_nd, (void *)s->tree_nx, (void *)s->tree_dp, (void *)s->tree_qm, s->tree_tmp,
+                    (void *)s->tree_stats})
         (void)hipFree(q);
     if (s->tree_host) (void)hipHostFree(s->tree_host);
     if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
@@ -952,6 +955,10 @@ static int tree_alloc(nb_sim *s)
     HIPCHK(hipMalloc((void **)&s->tree_nd, s->tree_cap * sizeof(float4)));
     HIPCHK(hipMalloc((void **)&s->tree_nx, s->tree_cap * sizeof(uint32_t)));
     HIPCHK(hipMalloc((void **)&s->tree_dp, s->tree_cap));
+    if (s->tree_quad) {     // +16 B per node (+256 B per body); zeroed once: the build writes every record a walk can read
+        HIPCHK(hipMalloc((void **)&s->tree_qm, s->tree_cap * sizeof(float4)));
+        HIPCHK(hipMemsetAsync(s->tree_qm, 0, s->tree_cap * sizeof(float4), s->stream));
+    }
     size_t sort_bytes = 0, scan_bytes = 0;
     HIPCHK(nb_tree_sort_pairs(nullptr, sort_bytes, s->tree_k64[0], s->tree_k64[2], s->tree_v32[0], s->tree_v32[1], n, s->stream));
     HIPCHK(nb_tree_scan(nullptr, scan_bytes, s->tree_cnt, s->tree_base, n + 2, s->stream));
@@ -995,21 +1002,31 @@ static int launch_tree_force(nb_sim *s)
     tree_emit<<<g2, 256, 0, s->stream>>>(s->tree_uhi, s->tree_ulo, s->tree_ufirst, v2, pos, mass, s->tree_base, n, s->tree_root_dev, s->tree_cap,
                                          s->tree_nd, s->tree_nx, s->tree_dp, st, s->frame);
     const uint32_t gc = (uint32_t)std::min<uint64_t>((s->tree_cap + 255u) / 256u, 8u * (uint32_t)s->cus);
-    for (int level = TREE_DEPTH_CAP - 1; level >= 0; --level)
-        tree_com<<<gc, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, (uint32_t)level, st);
+    for (int level = TREE_DEPTH_CAP - 1; level >= 0; --level) {
+        if (s->tree_quad) tree_com<true><<<gc, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, (uint32_t)level, st, s->tree_qm);
+        else tree_com<false><<<gc, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, (uint32_t)level, st);
+    }
     HIPCHK(hipGetLastError());
     std::pair<hipEvent_t, hipEvent_t> pr;
     if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
     const float eps2 = s->p.eps * s->p.eps;
-    if (tree_walk_is_group(s)) {     // the group walk, then the few lanes that left it (nb_tree.hip.h): one "force kernel" interval
-        tree_walk_group<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
-                                                  s->tree_head, s->tree_uidx, s->tree_ufirst);
-        tree_walk_alone<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
-                                                  s->tree_head, s->tree_uidx, s->tree_ufirst);
+    const float4 *qm = s->tree_qm;
+    if (tree_walk_is_group(s) && s->tree_quad) {     // the same two launches with the moment array (NB_FLAG_TREE_QUADRUPOLE)
+        tree_walk_group<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
+                                                        s->tree_head, s->tree_uidx, s->tree_ufirst, qm);
+        tree_walk_alone<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
+                                                        s->tree_head, s->tree_uidx, s->tree_ufirst, qm);
+    } else if (tree_walk_is_group(s)) {     // the group walk, then the few lanes that left it (nb_tree.hip.h): one "force kernel" interval
+        tree_walk_group<false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
+                                                         s->tree_head, s->tree_uidx, s->tree_ufirst);
+        tree_walk_alone<false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
+                                                         s->tree_head, s->tree_uidx, s->tree_ufirst);
+    } else if (s->tree_quad) {              // (with NB_FLAG_TREE_LEAVES only, and here with the Quake rsqrt: nb_create)
+        tree_walk<RSQ_QUAKE, true, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st, qm);
     } else {
         with_flags([&](auto q, auto leaves) {
-            tree_walk<q ? RSQ_QUAKE : RSQ_EXACT, leaves><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2,
-                                                                                     (float2 *)s->acc, st);
+            tree_walk<q ? RSQ_QUAKE : RSQ_EXACT, leaves, false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2,
+                                                                                            (float2 *)s->acc, st);
         }, s->p.rsqrt_mode == NB_RSQRT_QUAKE, s->tree_leaves);
     }
     HIPCHK(hipGetLastError());
@@ -1146,7 +1163,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
         nb_set_error("nb_create: quake rsqrt / sequential order are fp32 (reference arithmetic) modes");
         return nullptr;
     }
-    if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED | NB_FLAG_TREE_LEAVES)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
+    if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED | NB_FLAG_TREE_LEAVES | NB_FLAG_TREE_QUADRUPOLE)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
     if (p.extras & ~(NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY | NB_EXTRA_COLLIDE)) { nb_set_error("nb_create: unknown bits in extras 0x%x", (unsigned)p.extras); return nullptr; }
     if (p.extras & NB_EXTRA_COLLIDE) {
         const char *why = p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
@@ -1158,6 +1175,13 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     }
     if (p.force != NB_FORCE_DIRECT && p.force != NB_FORCE_TREE) { nb_set_error("nb_create: bad force %d", p.force); return nullptr; }
     if (!(p.theta >= 0.0f) || !std::isfinite(p.theta)) { nb_set_error("nb_create: theta must be >= 0 and finite"); return nullptr; }
+    if ((p.flags & NB_FLAG_TREE_QUADRUPOLE) && (p.force != NB_FORCE_TREE || !(p.flags & NB_FLAG_TREE_LEAVES))) {
+        nb_set_error("nb_create: NB_FLAG_TREE_QUADRUPOLE %s: the flag adds the second moment of an accepted cell to the convergent Barnes-Hut "
+                     "force (NB_FORCE_TREE with NB_FLAG_TREE_LEAVES)",
+                     p.force == NB_FORCE_TREE ? "without NB_FLAG_TREE_LEAVES" : (p.flags & NB_FLAG_TREE_LEAVES) ? "with NB_FORCE_DIRECT"
+                                                : "with NB_FORCE_DIRECT and without NB_FLAG_TREE_LEAVES");
+        return nullptr;
+    }
     if ((p.flags & NB_FLAG_TREE_LEAVES) && p.force != NB_FORCE_TREE) {
         nb_set_error("nb_create: NB_FLAG_TREE_LEAVES with NB_FORCE_DIRECT: the flag selects a walk of the Barnes-Hut force (NB_FORCE_TREE)");
         return nullptr;
@@ -1247,6 +1271,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     s->tree = p.force == NB_FORCE_TREE;
     s->tree_theta2 = p.theta * p.theta;
     s->tree_leaves = s->tree && (p.flags & NB_FLAG_TREE_LEAVES) != 0;
+    s->tree_quad = s->tree_leaves && (p.flags & NB_FLAG_TREE_QUADRUPOLE) != 0;
     if ((e = hipMalloc(&s->mass, n * s->rsz)) != hipSuccess) return fail("hipMalloc mass", e);
     if ((e = hipMalloc((void **)&s->radius, n * sizeof(float))) != hipSuccess) return fail("hipMalloc radius", e);
     if ((e = hipMalloc(&s->vel, s->i_count * r2)) != hipSuccess) return fail("hipMalloc vel", e);
@@ -2258,9 +2283,10 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
                  s->coll_large_n, (unsigned long long)s->coll_cap, resolve);
     const size_t len = strlen(buf);
     if (len < buflen) {
-        if (s->tree) snprintf(buf + len, buflen - len, " | force=tree theta=%.6g node_capacity=%llu depth_cap=%d%s", (double)s->p.theta,
+        if (s->tree) snprintf(buf + len, buflen - len, " | force=tree theta=%.6g node_capacity=%llu depth_cap=%d%s%s", (double)s->p.theta,
                               (unsigned long long)s->tree_cap, TREE_DEPTH_CAP,
-                              !s->tree_leaves ? "" : tree_walk_is_group(s) ? " leaves=1 walk=group" : " leaves=1 walk=lane");
+                              !s->tree_leaves ? "" : tree_walk_is_group(s) ? " leaves=1 walk=group" : " leaves=1 walk=lane",
+                              s->tree_quad ? " quad=1" : "");
         else snprintf(buf + len, buflen - len, " | force=direct");
     }
     return NB_OK;

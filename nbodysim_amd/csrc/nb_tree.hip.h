@@ -16,7 +16,8 @@
 //                             not separated within the cap: the build fails (reported like a collision overflow)
 //   tree_count + scan         nodes each point contributes to the pre-order layout (below) -> its first node index
 //   tree_emit                 writes the nodes: record {com.x, com.y, mass, size^2}, next (= index + subtree size), depth
-//   tree_com (per level)      centres of mass bottom-up, children 0..3 in order (Quadtree.hpp:236-258)
+//   tree_com (per level)      centres of mass bottom-up, children 0..3 in order (Quadtree.hpp:236-258); with
+//                             NB_FLAG_TREE_QUADRUPOLE also the second moments about them (tree_com<true>, below)
 //   tree_walk                 Quadtree::acc per body, bodies in key order so that a wave's lanes walk neighbouring paths
 //   tree_integrate            kick_drift_one (nb_kernels.hip.h) unless the build failed
 //
@@ -303,11 +304,22 @@ void tree_emit(const uint64_t *__restrict__ uhi, const uint64_t *__restrict__ ul
 }
 
 // Centres of mass of the branches of depth `level` (launched for level = TREE_DEPTH_CAP - 1 ... 0): Quadtree.hpp:236-258.
+// QUAD (NB_FLAG_TREE_QUADRUPOLE; the one trailing argument is then the moment array, one {xx, xy, yy, 0} per node, +16 B per node =
+// +256 B per body on top of the 535 B of a tree handle, allocated for such a handle only): the raw second moment
+// M = sum m_k (y_k - c)(y_k - c)^T of the branch about the centre of mass c just stored, from its children's moments (the earlier
+// launch) moved to c by the parallel-axis term, children 0..3 in order, no contraction (tests/tree_quad_model.py restates it bit
+// for bit).  A leaf or an empty quadrant has M = 0: the pass writes its record when it visits the parent.
+__device__ __forceinline__ float4 *tree_moments() { return nullptr; }
+__device__ __forceinline__ float4 *tree_moments(float4 *qm) { return qm; }
+__device__ __forceinline__ const float4 *tree_moments(const float4 *qm) { return qm; }
+
+template <bool QUAD, typename... M>
 __global__ __launch_bounds__(256)
 void tree_com(float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint8_t *__restrict__ dp, uint32_t level,
-              const TreeStats *__restrict__ st)
+              const TreeStats *__restrict__ st, M... moments)
 {
 #pragma clang fp contract(off)
+    static_assert(sizeof...(M) == (QUAD ? 1 : 0), "the moment array is the argument of the QUAD form alone");
     if (st->fail || level >= st->max_depth) return;
     const uint32_t total = (uint32_t)st->nodes;
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
@@ -326,6 +338,22 @@ void tree_com(float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const ui
             sx = sx * inv; sy = sy * inv;
         }
         nd[i] = make_float4(sx, sy, sm, nd[i].w);
+        if constexpr (QUAD) {
+            float4 *__restrict__ qm = tree_moments(moments...);
+            float xx = 0.f, xy = 0.f, yy = 0.f;
+            c = i + 1u;
+            for (int q = 0; q < 4 && c < total; ++q) {
+                const float4 ch = nd[c];
+                float4 mc = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (dp[c] & TREE_BRANCH) mc = qm[c]; else qm[c] = mc;
+                const float ex = ch.x - sx, ey = ch.y - sy;
+                xx = xx + (mc.x + ch.z * (ex * ex));
+                xy = xy + (mc.y + ch.z * (ex * ey));
+                yy = yy + (mc.z + ch.z * (ey * ey));
+                c = nx[c];
+            }
+            qm[i] = make_float4(xx, xy, yy, 0.f);
+        }
     }
 }
 
@@ -337,11 +365,41 @@ void tree_com(float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const ui
 // LEAVES (NB_FLAG_TREE_LEAVES): a leaf that is not accepted adds its own term (its record is exact: one position, the summed
 // mass), so every inserted body is counted once, in an accepted cell or as its leaf, and theta -> 0 is the direct sum.  The
 // nodes visited are the same; an empty quadrant (mass 0) adds nothing and costs no rsqrt.
-template <int RSQ, bool LEAVES>
+// QUAD (NB_FLAG_TREE_QUADRUPOLE, with LEAVES; the one trailing argument is then tree_com<true>'s moment array): an accepted BRANCH
+// adds, with d = com - body, R^2 = d^2 + eps^2, M its raw second moment,
+//     d * (m R^-3 + 7.5 (d^T M d) R^-7 - 1.5 tr(M) R^-5) - 3 (M d) R^-5
+// (the second-order term of the softened potential about the centre of mass; the dipole vanishes there).  The record is loaded on
+// acceptance of a branch only; the nodes visited and the acceptance test are unchanged, and a leaf's term, accepted or not, is
+// the monopole term above, instruction for instruction.
+template <int RSQ>
+__device__ __forceinline__ void tree_quad_term(float4 q, float4 m, float dx, float dy, float d2, float eps2, float &sx, float &sy)
+{
+    if constexpr (RSQ == RSQ_QUAKE) {
+#pragma clang fp contract(off)
+        const float inv = quake_rsqrt(d2 + eps2);
+        const float inv2 = inv * inv, inv3 = inv2 * inv, inv5 = inv3 * inv2, inv7 = inv5 * inv2;
+        const float ux = m.x * dx + m.y * dy, uy = m.y * dx + m.z * dy;
+        const float rMr = dx * ux + dy * uy, tr = m.x + m.z;
+        const float g = q.z * inv3 + (7.5f * (rMr * inv7) - 1.5f * (tr * inv5));
+        sx = sx + (dx * g - 3.0f * (ux * inv5));
+        sy = sy + (dy * g - 3.0f * (uy * inv5));
+    } else {
+        const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
+        const float inv2 = inv * inv, inv3 = inv2 * inv, inv5 = inv3 * inv2, inv7 = inv5 * inv2;
+        const float ux = m.x * dx + m.y * dy, uy = m.y * dx + m.z * dy;
+        const float rMr = dx * ux + dy * uy, tr = m.x + m.z;
+        const float g = q.z * inv3 + (7.5f * (rMr * inv7) - 1.5f * (tr * inv5));
+        sx = sx + (dx * g - 3.0f * (ux * inv5));
+        sy = sy + (dy * g - 3.0f * (uy * inv5));
+    }
+}
+
+template <int RSQ, bool LEAVES, bool QUAD, typename... M>
 __device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restrict__ nd, const uint32_t *__restrict__ nx,
                                               const uint32_t *__restrict__ val, const float2 *__restrict__ pos, float eps2, float theta2,
-                                              float2 *__restrict__ acc, const TreeStats *__restrict__ st)
+                                              float2 *__restrict__ acc, const TreeStats *__restrict__ st, M... moments)
 {
+    static_assert(sizeof...(M) == (QUAD ? 1 : 0) && (LEAVES || !QUAD), "the moment array is the argument of the QUAD form alone");
     const uint32_t b = val[i];
     const float2 p = pos[b];
     const uint32_t total = (uint32_t)st->nodes;
@@ -373,9 +431,18 @@ __device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restri
             }
         };
         if (far) {
-            if (d2 > 0.f) term();
-            const uint32_t next = nx[node];
-            node = next > node ? next : node + 1u;           // (next > node always; the walk ends whatever the array holds)
+            if constexpr (QUAD) {
+                const uint32_t next = nx[node];
+                if (d2 > 0.f) {
+                    if (next == node + 1u) term();
+                    else tree_quad_term<RSQ>(q, tree_moments(moments...)[node], dx, dy, d2, eps2, sx, sy);
+                }
+                node = next > node ? next : node + 1u;
+            } else {
+                if (d2 > 0.f) term();
+                const uint32_t next = nx[node];
+                node = next > node ? next : node + 1u;       // (next > node always; the walk ends whatever the array holds)
+            }
         } else {
             if constexpr (LEAVES) {
                 if (q.z != 0.f && d2 > 0.f && nx[node] == node + 1u) term();
@@ -386,15 +453,15 @@ __device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restri
     acc[b] = make_float2(sx, sy);
 }
 
-template <int RSQ, bool LEAVES>
+template <int RSQ, bool LEAVES, bool QUAD, typename... M>
 __global__ __launch_bounds__(256)
 void tree_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
-               const TreeStats *__restrict__ st)
+               const TreeStats *__restrict__ st, M... moments)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || st->fail) return;
-    tree_walk_one<RSQ, LEAVES>(i, nd, nx, val, pos, eps2, theta2, acc, st);
+    tree_walk_one<RSQ, LEAVES, QUAD>(i, nd, nx, val, pos, eps2, theta2, acc, st, moments...);
 }
 
 // The wave-uniform walk of NB_FLAG_TREE_LEAVES with NB_RSQRT_EXACT: one wave is one group, the 64 bodies at sorted positions
@@ -407,6 +474,8 @@ void tree_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, c
 // of lane would make it: massless bodies (they sort last, by index alone) and a body on a position that first appears in an
 // earlier group (which of the bodies sharing the position falls behind the boundary follows the index).  These lanes leave
 // the group walk (tree_lane_alone) and tree_walk_alone gives each of them its own per-lane walk afterwards.
+// QUAD: `all_far` and `leaf` are the same in every lane, so the moment record of an accepted branch is loaded inside that
+// wave-uniform branch, by the readfirstlane node index: once per wave, through the scalar path, and for accepted branches only.
 __device__ __forceinline__ bool tree_lane_alone(uint32_t i, const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
                                                 const uint32_t *__restrict__ ufirst, const TreeStats *__restrict__ st)
 {
@@ -415,23 +484,26 @@ __device__ __forceinline__ bool tree_lane_alone(uint32_t i, const uint32_t *__re
     return (ufirst[(uint32_t)uidx[i] - 1u] >> 6) != (i >> 6);        // (not a head: at least one key starts before i)
 }
 
+template <bool QUAD, typename... M>
 __global__ __launch_bounds__(256)
 void tree_walk_alone(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                      const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
                      const TreeStats *__restrict__ st, const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
-                     const uint32_t *__restrict__ ufirst)
+                     const uint32_t *__restrict__ ufirst, M... moments)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || st->fail || !tree_lane_alone(i, head, uidx, ufirst, st)) return;
-    tree_walk_one<RSQ_EXACT, true>(i, nd, nx, val, pos, eps2, theta2, acc, st);
+    tree_walk_one<RSQ_EXACT, true, QUAD>(i, nd, nx, val, pos, eps2, theta2, acc, st, moments...);
 }
 
+template <bool QUAD, typename... M>
 __global__ __launch_bounds__(256)
 void tree_walk_group(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                      const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
                      const TreeStats *__restrict__ st, const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
-                     const uint32_t *__restrict__ ufirst)
+                     const uint32_t *__restrict__ ufirst, M... moments)
 {
+    static_assert(sizeof...(M) == (QUAD ? 1 : 0), "the moment array is the argument of the QUAD form alone");
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || st->fail || tree_lane_alone(i, head, uidx, ufirst, st)) return;
     const uint32_t b = val[i];
@@ -453,7 +525,19 @@ void tree_walk_group(const float4 *__restrict__ nd, const uint32_t *__restrict__
         }
         const bool all_far = __ballot(!far) == 0ull;
         const bool leaf = next == node + 1u;
-        if (all_far || (leaf && q.z != 0.f)) {
+        if constexpr (QUAD) {
+            if (all_far && !leaf) {
+                const float4 m = tree_moments(moments...)[node];
+                if (d2 > 0.f) tree_quad_term<RSQ_EXACT>(q, m, dx, dy, d2, eps2, sx, sy);
+            } else if (leaf && (all_far || q.z != 0.f)) {
+                if (d2 > 0.f) {
+                    const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
+                    const float s = q.z * (inv * inv * inv);
+                    sx = __builtin_fmaf(dx, s, sx);
+                    sy = __builtin_fmaf(dy, s, sy);
+                }
+            }
+        } else if (all_far || (leaf && q.z != 0.f)) {
             if (d2 > 0.f) {
                 const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
                 const float s = q.z * (inv * inv * inv);

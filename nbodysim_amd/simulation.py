@@ -72,6 +72,7 @@ class Simulation:
         theta: float = 1.0,
         library=None,
         tree_leaves: bool = False,
+        tree_quadrupole: bool = False,
     ):
         """The last arguments (from ``uniform_mass`` on) are ``nb_params.flags`` and the launch-geometry tuning fields
         (0 / True = the library's automatic choice); the library reads no environment variables.  ``mass_scaling``: False / None
@@ -81,10 +82,15 @@ class Simulation:
         hard-sphere collisions (adds NB_EXTRA_COLLIDE to ``extras``; unsharded 2-D kick-drift only).  ``force``: "direct" (every pair) or "tree" (the reference's
         Barnes-Hut quadtree with opening parameter ``theta``, NB_FORCE_TREE; unsharded 2-D fp32 kick-drift only).  ``tree_leaves``
         (``force="tree"`` only, ValueError otherwise): the convergent tree force, NB_FLAG_TREE_LEAVES — leaves that are not accepted
-        contribute, so the result tends to the direct sum as ``theta`` -> 0; not the reference's arithmetic.  ``library``: another
+        contribute, so the result tends to the direct sum as ``theta`` -> 0; not the reference's arithmetic.  ``tree_quadrupole``
+        (``force="tree"`` with ``tree_leaves=True`` only, ValueError otherwise): accepted cells add their second moment,
+        NB_FLAG_TREE_QUADRUPOLE — the same walk, a smaller error at the same ``theta``, +256 bytes per body.  ``library``: another
         build of the library bound with ``_lib.bind`` (the tests' -DNB_TEST_HOOKS build); default the product."""
         if tree_leaves and force != "tree":
             raise ValueError('tree_leaves=True needs force="tree" (NB_FLAG_TREE_LEAVES selects a walk of the Barnes-Hut force)')
+        if tree_quadrupole and not (force == "tree" and tree_leaves):
+            raise ValueError('tree_quadrupole=True needs force="tree" and tree_leaves=True (NB_FLAG_TREE_QUADRUPOLE adds a term to the '
+                             "accepted cells of the convergent Barnes-Hut force)")
         lib = library if library is not None else L.load()
         if bodies.dtype not in (L.BODY_DTYPE, L.BODY3_DTYPE):
             raise TypeError("bodies must be a numpy array of nbodysim_amd.BODY_DTYPE (64-byte Body records)")
@@ -114,7 +120,8 @@ class Simulation:
                    | (L.NB_FLAG_SHARD_SINGLE if shard_single else 0)
                    | (L.NB_FLAG_MASS_SCALING_MEASURED if mass_scaling == "measured" else L.NB_FLAG_MASS_SCALING if mass_scaling is True
                       else L.NB_FLAG_NO_MASS_SCALING if mass_scaling is False else 0)
-                   | (L.NB_FLAG_STATIC_ITEMS if static_items else 0) | (L.NB_FLAG_TREE_LEAVES if tree_leaves else 0))
+                   | (L.NB_FLAG_STATIC_ITEMS if static_items else 0) | (L.NB_FLAG_TREE_LEAVES if tree_leaves else 0)
+                   | (L.NB_FLAG_TREE_QUADRUPOLE if tree_quadrupole else 0))
         p.sym_chunks_per_item, p.sym_aux_stream, p.sym_late_us, p.lanes_p = sym_chunks_per_item, sym_aux_stream, sym_late_us, lanes_p
         if sym_tail is not None:
             p.sym_tail[0], p.sym_tail[1], p.sym_tail[2] = sym_tail

@@ -13,10 +13,18 @@ last build, and direct / tree.
     python tools/tree_bench.py --theta T [--leaves] [case ...]      the walk alone, hardware rsqrt, opening parameter T, with
                                                --leaves the convergent force (NB_FLAG_TREE_LEAVES); cases 262144 and 1048576 by default
 
+    python tools/tree_bench.py --theta T --leaves --quad [case ...]  the same with the quadrupole term (NB_FLAG_TREE_QUADRUPOLE)
+    python tools/tree_bench.py --sweep [case ...]                   the convergent force at theta 1.0, 0.7, 0.5, 0.3, each without and
+                                               with the quadrupole term: one line per (case, theta, quad), then per case the
+                                               equal-accuracy pairs (for each monopole theta the largest quadrupole theta whose
+                                               median error is no worse)
+
 With --theta the handle steps for at least 2 s, then FIVE stretches are timed; per stretch the milliseconds per step (host clock
 between two waits) and the milliseconds per walk (nb_profile_read, device events around the walk).  One JSON line per case: the
-five figures of each, their median and spread (max - min), and the walk nb_describe names.  A library built from another commit
-is measured through NBODY_HIP_LIB (the cases without --leaves need nothing this tool adds).
+five figures of each, their median and spread (max - min), and the walk nb_describe names.  With --leaves the line also carries
+the median and the 99th percentile of the per-body error of the INITIAL accelerations, |a - a_direct| / |a_direct|, against a
+direct-sum handle (hardware rsqrt) on the same bodies.  A library built from another commit is measured through NBODY_HIP_LIB
+(the cases without --leaves need nothing this tool adds).
 """
 from __future__ import annotations
 
@@ -55,13 +63,26 @@ def settled_ms(sim, dt: float, warm_s: float = 2.0, timed_s: float = 1.0) -> flo
     return (time.perf_counter() - t0) / k * 1e3
 
 
-def run_walk(case: str, theta: float, leaves: bool, stretches: int = 5, timed_s: float = 1.0) -> dict:
+def direct_accelerations(case: str):
+    """The initial accelerations of the case's bodies from a direct-sum handle (hardware rsqrt), as float64."""
+    with nb.Simulation(nb.plummer_2d(int(case), 42), rsqrt="exact", eps=0.01, device=0) as sim:
+        return sim.accelerations().astype("float64")
+
+
+def run_walk(case: str, theta: float, leaves: bool, stretches: int = 5, timed_s: float = 1.0, quad: bool = False, direct=None) -> dict:
     bodies, dt = nb.plummer_2d(int(case), 42), 1e-3
     kw = dict(tree_leaves=True) if leaves else {}
+    if quad:
+        kw["tree_quadrupole"] = True
     with nb.Simulation(bodies, force="tree", rsqrt="exact", theta=theta, eps=0.01, device=0, **kw) as sim:
         d = sim.describe()
-        out = {"case": case, "n": int(bodies.shape[0]), "theta": theta, "leaves": int(leaves),
+        out = {"case": case, "n": int(bodies.shape[0]), "theta": theta, "leaves": int(leaves), "quad": int(quad),
                "walk": d.split(" walk=")[1].split()[0] if " walk=" in d else "lane"}
+        if direct is not None:
+            a = sim.accelerations().astype("float64")
+            mag = (direct[:, 0] ** 2 + direct[:, 1] ** 2) ** 0.5
+            err = sorted(((a[:, 0] - direct[:, 0]) ** 2 + (a[:, 1] - direct[:, 1]) ** 2) ** 0.5 / mag)
+            out["err_median"], out["err_p99"] = float(f"{err[len(err) // 2]:.3e}"), float(f"{err[len(err) * 99 // 100]:.3e}")
         est = settle(sim, dt)
         k = max(3, min(int(timed_s / est), 5000))
         step_ms, walk_ms = [], []
@@ -120,19 +141,44 @@ def trace(case: str, steps: int = 50) -> None:
     print(json.dumps({"case": case, "traced_steps": steps}))
 
 
+def sweep(cases, thetas=(1.0, 0.7, 0.5, 0.3)) -> None:
+    for c in cases:
+        direct = direct_accelerations(c)
+        rows = {}
+        for theta in thetas:
+            for quad in (False, True):
+                rows[theta, quad] = run_walk(c, theta, True, quad=quad, direct=direct)
+                print(json.dumps(rows[theta, quad]), flush=True)
+        for theta in thetas:                                 # equal accuracy: the largest quadrupole theta that is no worse
+            mono = rows[theta, False]
+            ok = [t for t in thetas if rows[t, True]["err_median"] <= mono["err_median"]]
+            if not ok:
+                continue
+            q = rows[max(ok), True]
+            print(json.dumps({"case": c, "equal_accuracy": {"monopole_theta": theta, "quadrupole_theta": max(ok)},
+                              "err_median": [mono["err_median"], q["err_median"]],
+                              "walk_ms": [mono["walk_ms_median"], q["walk_ms_median"]], "step_ms": [mono["step_ms_median"], q["step_ms_median"]],
+                              "walk_ms_spread": [mono["walk_ms_spread"], q["walk_ms_spread"]],
+                              "step_ms_spread": [mono["step_ms_spread"], q["step_ms_spread"]]}), flush=True)
+
+
 if __name__ == "__main__":
     if sys.argv[1:2] == ["--trace"]:
         trace(sys.argv[2])
+        sys.exit(0)
+    if sys.argv[1:2] == ["--sweep"]:
+        sweep(sys.argv[2:] or ["262144", "1048576"])
         sys.exit(0)
     if "--theta" in sys.argv:
         args = sys.argv[1:]
         theta = float(args.pop(args.index("--theta") + 1))
         args.remove("--theta")
-        leaves = "--leaves" in args
-        if leaves:
-            args.remove("--leaves")
+        leaves, quad = "--leaves" in args, "--quad" in args
+        for flag in ("--leaves", "--quad"):
+            if flag in args:
+                args.remove(flag)
         for c in args or ["262144", "1048576"]:
-            print(json.dumps(run_walk(c, theta, leaves)), flush=True)
+            print(json.dumps(run_walk(c, theta, leaves, quad=quad, direct=direct_accelerations(c) if leaves else None)), flush=True)
         sys.exit(0)
     for c in sys.argv[1:] or ["default", "262144", "1048576", "8388608"]:
         print(json.dumps(run(c)), flush=True)
