@@ -134,7 +134,9 @@ enum { NB_FORCE_DIRECT = 0,    /* every pair: the kernels this library is built 
                                   stay; with NB_EXTRA_COLLIDE the collision pass of that step still runs, on the unchanged
                                   positions), and the next synchronising call (nb_wait, nb_sync, nb_sync_positions, nb_energy,
                                   nb_momentum, nb_tree_stats) returns NB_ENOMEM once, naming the frame and what was needed.
-                                  nb_energy / nb_momentum stay the exact O(n^2) / O(n) diagnostics */
+                                  nb_momentum stays the exact O(n) diagnostic.  nb_energy is the exact O(n^2) fp64 pair sweep of a
+                                  direct-sum handle (at the sizes the tree exists for one reading costs as much as many steps)
+                                  unless the handle has NB_FLAG_TREE_ENERGY (flags, below): it then walks the tree, O(n log n) */
 
 /* integrator */
 enum { NB_INTEGRATOR_KICK_DRIFT = 0, /* Simulation.hpp:129-131,160-163 (reference) */
@@ -177,7 +179,7 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          NB_FLAG_SHARD_ALLREDUCE, the replicated one) with ONE rank — every pair is "local",
                                          the reduce-scatter / all-gather degenerate to copies.  For rehearsing the exchange
                                          path (nb_comm_*, nb_exchange_*) on a single GPU; never faster than a plain handle */
-       /* 2048 is unassigned (4096 and 8192 are the two tree bits below): nb_create rejects it like any unknown bit */
+       /* 2048 is unassigned (4096, 8192 and 16384 are the three tree bits below): nb_create rejects it like any unknown bit */
        NB_FLAG_TREE_LEAVES     = 4096,  /* NB_FORCE_TREE only (with NB_FORCE_DIRECT nb_create returns NB_EINVAL, naming the combination):
                                          the CONVERGENT Barnes-Hut force.  Cells, centres of mass, node order and the acceptance test
                                          size^2 < d^2 * theta^2 are those of NB_FORCE_TREE without the bit; a leaf that is not accepted adds
@@ -195,7 +197,7 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          window walk on their own).  Deterministic either way: two handles agree bit for bit, and permuting
                                          the bodies permutes the bits.  nb_describe appends " leaves=1 walk=lane|group".
                                          Everything the handle refuses or ignores as a tree handle it refuses or ignores with the bit too */
-       NB_FLAG_TREE_QUADRUPOLE = 8192 };/* NB_FORCE_TREE with NB_FLAG_TREE_LEAVES only (alone, with NB_FORCE_DIRECT or without
+       NB_FLAG_TREE_QUADRUPOLE = 8192,  /* NB_FORCE_TREE with NB_FLAG_TREE_LEAVES only (alone, with NB_FORCE_DIRECT or without
                                          NB_FLAG_TREE_LEAVES nb_create returns NB_EINVAL, naming the flag and the missing partner): accepted
                                          cells carry the next multipole term.  Every branch keeps, beside its centre of mass c, the raw second
                                          moment M = sum m_k (y_k - c)(y_k - c)^T over the inserted positions of its subtree (xx, xy, yy; raw,
@@ -216,6 +218,31 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          per body of a tree handle, allocated only with the bit.  nb_describe appends " quad=1" after
                                          "walk=...".  Without the bit nothing changes: same bits, same launches, same memory.  Everything a
                                          NB_FLAG_TREE_LEAVES handle refuses or ignores it refuses or ignores with the bit too */
+       NB_FLAG_TREE_ENERGY = 16384 };   /* NB_FORCE_TREE with NB_FLAG_TREE_LEAVES only, with or without NB_FLAG_TREE_QUADRUPOLE (with
+                                         NB_FORCE_DIRECT or without NB_FLAG_TREE_LEAVES nb_create returns NB_EINVAL, naming the flag and the
+                                         missing or conflicting partner; a walk without the leaves has no near field and no meaningful
+                                         potential): nb_energy becomes an O(n log n) diagnostic.  It rebuilds the tree at the current
+                                         positions and walks it: *potential = 1/2 sum m_i phi_i, phi_i summed over exactly the nodes the
+                                         wave-uniform force walk takes for body i (the fp32 acceptance test, windows of 64 bodies in key
+                                         order, the "walks alone" rule), whatever rsqrt_mode the handle has: the potential has one walk.
+                                         With d = c - body position and R^2 = d^2 + eps^2 a leaf, or an accepted cell without
+                                         NB_FLAG_TREE_QUADRUPOLE, adds -m / R; an accepted branch with it adds
+                                             -(m / R + 1.5 (d^T M d) / R^5 - 0.5 tr(M) / R^3)
+                                         (the potential whose gradient is the force term above).  Node records, moments and positions are
+                                         the fp32 values of the build, except that a leaf holding several bodies weighs the fp64 sum of
+                                         their masses (its fp32 record plus an fp32 residual kept per node for this walk; +4 bytes per
+                                         node); every term, the per-body sums and the reductions are fp64.
+                                         *kinetic is sum m v^2 / 2 as before.  THE SAME PAIRS as nb_energy without the flag: every unordered
+                                         pair once, the bodies sharing one position included (-m_i m_j / eps each, added body by body, not
+                                         from the leaf's fp32 mass sum); massless bodies weigh nothing; theta = 0 IS the direct energy.
+                                         ONE DIFFERENCE: with eps = 0 the pairs on one position are skipped and the result is finite,
+                                         where the direct form gives inf.  No effect on the trajectory: acc[], positions, velocities and
+                                         the frame counter are untouched; the tree arrays are rebuilt (the next force evaluation rebuilds
+                                         them anyway) and nb_tree_stats then describes this build.  A build that fails (node capacity,
+                                         depth cap) makes THIS call return NB_ENOMEM, through the once-only report above, and *kinetic /
+                                         *potential are not written.  nb_describe appends " energy=tree".  Without the bit nb_energy is
+                                         unchanged on every kind of handle.  +64 bytes per body (the leaf residuals) and +16 bytes per 256
+                                         bodies (the partials of the second launch) */
 
 /* ---- parameters ----------------------------------------------------------- */
 typedef struct nb_params {

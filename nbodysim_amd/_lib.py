@@ -35,6 +35,7 @@ NB_FLAG_NO_MASS_SCALING = 512
 NB_FLAG_MASS_SCALING_MEASURED = 1024
 NB_FLAG_TREE_LEAVES = 4096           # (2048 is unassigned)
 NB_FLAG_TREE_QUADRUPOLE = 8192       # with NB_FORCE_TREE and NB_FLAG_TREE_LEAVES only
+NB_FLAG_TREE_ENERGY = 16384          # with NB_FORCE_TREE and NB_FLAG_TREE_LEAVES only: nb_energy walks the tree
 
 #: numpy view of the reference's 64-byte ``Body`` record (Body.hpp:6-13, Vec2.hpp:17-20)
 BODY_DTYPE = np.dtype(

@@ -174,6 +174,7 @@ struct nb_sim {
     float tree_theta2 = 1.0f;                  // theta * theta, Quadtree.hpp:18
     bool tree_leaves = false;                  // NB_FLAG_TREE_LEAVES: leaves that are not accepted contribute
     bool tree_quad = false;                    // NB_FLAG_TREE_QUADRUPOLE: accepted branches add their second moment
+    bool tree_energy = false;                  // NB_FLAG_TREE_ENERGY: nb_energy walks the tree (ered_dev then holds 4 x ered_blocks)
     uint64_t tree_cap = 0;                     // node capacity: nodes allocated
     uint64_t tree_ovf_reported = 0;            // failed evaluations already reported by a synchronising call
     uint64_t *tree_k64[4] = {nullptr, nullptr, nullptr, nullptr};   // key words by body: high, low; two sort buffers
@@ -190,6 +191,7 @@ struct nb_sim {
     uint32_t *tree_nx = nullptr;               // next: index + subtree size
     uint8_t *tree_dp = nullptr;                // depth | TREE_BRANCH
     float4 *tree_qm = nullptr;                 // second moments {xx, xy, yy, 0} per node: NB_FLAG_TREE_QUADRUPOLE handles only
+    float *tree_lo = nullptr;                  // float64 mass sum - record mass per leaf with bodies: NB_FLAG_TREE_ENERGY handles only
     void *tree_tmp = nullptr;                  // rocprim temporary storage (sort, scan)
     size_t tree_tmp_bytes = 0;
     TreeStats *tree_stats = nullptr;           // device
@@ -691,7 +693,7 @@ static void free_all(nb_sim *s)
     for (void *q : {(void *)s->tree_k64[0], (void *)s->tree_k64[1], (void *)s->tree_k64[2], (void *)s->tree_k64[3], (void *)s->tree_v32[0],
                     (void *)s->tree_v32[1], (void *)s->tree_v32[2], (void *)s->tree_head, (void *)s->tree_uidx, (void *)s->tree_uhi,
                     (void *)s->tree_ulo, (void *)s->tree_ufirst, (void *)s->tree_cnt, (void *)s->tree_base, (void *)s->tree_part,
-                    (void *)s->tree_root_dev, (void *)s->tree_nd, (void *)s->tree_nx, (void *)s->tree_dp, (void *)s->tree_qm, s->tree_tmp,
+                    (void *)s->tree_root_dev, (void *)s->tree_nd, (void *)s->tree_nx, (void *)s->tree_dp, (void *)s->tree_qm, (void *)s->tree_lo, s->tree_tmp,
                     (void *)s->tree_stats})
         (void)hipFree(q);
     if (s->tree_host) (void)hipHostFree(s->tree_host);
@@ -959,6 +961,7 @@ static int tree_alloc(nb_sim *s)
         HIPCHK(hipMalloc((void **)&s->tree_qm, s->tree_cap * sizeof(float4)));
         HIPCHK(hipMemsetAsync(s->tree_qm, 0, s->tree_cap * sizeof(float4), s->stream));
     }
+    if (s->tree_energy) HIPCHK(hipMalloc((void **)&s->tree_lo, s->tree_cap * sizeof(float)));   // +4 B per node; written per build
     size_t sort_bytes = 0, scan_bytes = 0;
     HIPCHK(nb_tree_sort_pairs(nullptr, sort_bytes, s->tree_k64[0], s->tree_k64[2], s->tree_v32[0], s->tree_v32[1], n, s->stream));
     HIPCHK(nb_tree_scan(nullptr, scan_bytes, s->tree_cnt, s->tree_base, n + 2, s->stream));
@@ -975,8 +978,9 @@ static int tree_alloc(nb_sim *s)
 // model restates bit for bit) with the Quake rsqrt.
 static bool tree_walk_is_group(const nb_sim *s) { return s->tree_leaves && s->p.rsqrt_mode != NB_RSQRT_QUAKE; }
 
-// One force evaluation at pos[cur] into acc[] (nb_tree.hip.h has the pipeline).  The walk is "the force kernel" of nb_profile_read.
-static int launch_tree_force(nb_sim *s)
+// The tree of pos[cur] (nb_tree.hip.h has the pipeline): bounds ... tree_com.  A force evaluation and, on a NB_FLAG_TREE_ENERGY
+// handle, nb_energy start with it.
+static int launch_tree_build(nb_sim *s)
 {
     const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u, g2 = (n + 2u + 255u) / 256u;
     const float2 *pos = (const float2 *)s->pos[s->cur];
@@ -1007,6 +1011,17 @@ static int launch_tree_force(nb_sim *s)
         else tree_com<false><<<gc, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, (uint32_t)level, st);
     }
     HIPCHK(hipGetLastError());
+    return NB_OK;
+}
+
+// One force evaluation at pos[cur] into acc[]: the build, then the walk.  The walk is "the force kernel" of nb_profile_read.
+static int launch_tree_force(nb_sim *s)
+{
+    { const int rc = launch_tree_build(s); if (rc) return rc; }
+    const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u;
+    const float2 *pos = (const float2 *)s->pos[s->cur];
+    uint32_t *v2 = s->tree_v32[2];
+    TreeStats *st = s->tree_stats;
     std::pair<hipEvent_t, hipEvent_t> pr;
     if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
     const float eps2 = s->p.eps * s->p.eps;
@@ -1031,6 +1046,38 @@ static int launch_tree_force(nb_sim *s)
     }
     HIPCHK(hipGetLastError());
     if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
+    return NB_OK;
+}
+
+// nb_energy of a NB_FLAG_TREE_ENERGY handle: the tree of the current positions, the float64 mass residuals of its leaves, then the
+// potential walk (nb_tree.hip.h): the
+// windows into partials [0, g) (K) and [g, 2g) (U), the lanes that left them into [2g, 3g) and [3g, 4g).  Touches neither acc[]
+// nor the state; the tree arrays are this build's afterwards.
+static int launch_tree_potential(nb_sim *s)
+{
+    { const int rc = launch_tree_build(s); if (rc) return rc; }
+    const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u;
+    const float2 *pos = (const float2 *)s->pos[s->cur], *vel = (const float2 *)s->vel;
+    const float *mass = (const float *)s->mass;
+    const uint32_t *v2 = s->tree_v32[2];
+    const TreeStats *st = s->tree_stats;
+    const double eps2 = (double)s->p.eps * (double)s->p.eps;
+    double *e = s->ered_dev;
+    const float4 *qm = s->tree_qm;
+    const float *lo = s->tree_lo;
+    tree_leaf_residual<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_base, s->tree_ufirst, v2, mass, n, st, s->tree_lo);
+    if (s->tree_quad) {
+        tree_potential_group<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
+                                                             s->tree_uidx, s->tree_ufirst, e, e + g, lo, qm);
+        tree_potential_alone<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
+                                                             s->tree_uidx, s->tree_ufirst, e + 2 * (size_t)g, e + 3 * (size_t)g, lo, qm);
+    } else {
+        tree_potential_group<false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
+                                                              s->tree_uidx, s->tree_ufirst, e, e + g, lo);
+        tree_potential_alone<false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
+                                                              s->tree_uidx, s->tree_ufirst, e + 2 * (size_t)g, e + 3 * (size_t)g, lo);
+    }
+    HIPCHK(hipGetLastError());
     return NB_OK;
 }
 
@@ -1163,7 +1210,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
         nb_set_error("nb_create: quake rsqrt / sequential order are fp32 (reference arithmetic) modes");
         return nullptr;
     }
-    if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED | NB_FLAG_TREE_LEAVES | NB_FLAG_TREE_QUADRUPOLE)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
+    if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED | NB_FLAG_TREE_LEAVES | NB_FLAG_TREE_QUADRUPOLE | NB_FLAG_TREE_ENERGY)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
     if (p.extras & ~(NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY | NB_EXTRA_COLLIDE)) { nb_set_error("nb_create: unknown bits in extras 0x%x", (unsigned)p.extras); return nullptr; }
     if (p.extras & NB_EXTRA_COLLIDE) {
         const char *why = p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
@@ -1175,6 +1222,13 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     }
     if (p.force != NB_FORCE_DIRECT && p.force != NB_FORCE_TREE) { nb_set_error("nb_create: bad force %d", p.force); return nullptr; }
     if (!(p.theta >= 0.0f) || !std::isfinite(p.theta)) { nb_set_error("nb_create: theta must be >= 0 and finite"); return nullptr; }
+    if ((p.flags & NB_FLAG_TREE_ENERGY) && (p.force != NB_FORCE_TREE || !(p.flags & NB_FLAG_TREE_LEAVES))) {
+        nb_set_error("nb_create: NB_FLAG_TREE_ENERGY %s: the flag makes nb_energy walk the tree of the convergent Barnes-Hut force "
+                     "(NB_FORCE_TREE with NB_FLAG_TREE_LEAVES; without the leaves a walk has no near field and no meaningful potential)",
+                     p.force == NB_FORCE_TREE ? "without NB_FLAG_TREE_LEAVES" : (p.flags & NB_FLAG_TREE_LEAVES) ? "with NB_FORCE_DIRECT"
+                                                : "with NB_FORCE_DIRECT and without NB_FLAG_TREE_LEAVES");
+        return nullptr;
+    }
     if ((p.flags & NB_FLAG_TREE_QUADRUPOLE) && (p.force != NB_FORCE_TREE || !(p.flags & NB_FLAG_TREE_LEAVES))) {
         nb_set_error("nb_create: NB_FLAG_TREE_QUADRUPOLE %s: the flag adds the second moment of an accepted cell to the convergent Barnes-Hut "
                      "force (NB_FORCE_TREE with NB_FLAG_TREE_LEAVES)",
@@ -1272,6 +1326,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     s->tree_theta2 = p.theta * p.theta;
     s->tree_leaves = s->tree && (p.flags & NB_FLAG_TREE_LEAVES) != 0;
     s->tree_quad = s->tree_leaves && (p.flags & NB_FLAG_TREE_QUADRUPOLE) != 0;
+    s->tree_energy = s->tree_leaves && (p.flags & NB_FLAG_TREE_ENERGY) != 0;
     if ((e = hipMalloc(&s->mass, n * s->rsz)) != hipSuccess) return fail("hipMalloc mass", e);
     if ((e = hipMalloc((void **)&s->radius, n * sizeof(float))) != hipSuccess) return fail("hipMalloc radius", e);
     if ((e = hipMalloc(&s->vel, s->i_count * r2)) != hipSuccess) return fail("hipMalloc vel", e);
@@ -1280,7 +1335,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     if ((e = hipMalloc(&s->partial, s->tree ? r2 : (size_t)s->slabs_cap * s->i_count * r2)) != hipSuccess) return fail("hipMalloc partial", e);
     if ((e = hipMalloc((void **)&s->aos_dev, n * sizeof(nb_body))) != hipSuccess) return fail("hipMalloc aos", e);
     s->ered_blocks = (s->i_count + BLOCK - 1) / BLOCK;
-    if ((e = hipMalloc((void **)&s->ered_dev, 2 * s->ered_blocks * sizeof(double))) != hipSuccess) return fail("hipMalloc energy", e);
+    if ((e = hipMalloc((void **)&s->ered_dev, (s->tree_energy ? 4 : 2) * s->ered_blocks * sizeof(double))) != hipSuccess) return fail("hipMalloc energy", e);
 
     if (symmetric(s) && plan_sym(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
     s->collide = (p.extras & NB_EXTRA_COLLIDE) != 0;
@@ -1928,6 +1983,18 @@ extern "C" int nb_energy(nb_sim *s, double *kinetic, double *potential)
     if (bind(s)) return NB_EHIP;
     { const int rc = step_check(s); if (rc) return rc; }
     const uint32_t g = (uint32_t)s->ered_blocks;
+    if (s->tree_energy) {       // O(n log n): the tree of the current positions and its potential walk; a failed build is reported by THIS call
+        { const int rc = launch_tree_potential(s); if (rc) return rc; }
+        { const int rc = tree_check(s); if (rc) return rc; }
+        std::vector<double> h(4 * (size_t)g);
+        { const int rc = copy_d2h(s, h.data(), s->ered_dev, h.size() * sizeof(double)); if (rc) return rc; }
+        double K = 0.0, U = 0.0;
+        for (uint32_t q = 0; q < 2; ++q)
+            for (uint32_t b = 0; b < g; ++b) { K += h[2 * (size_t)q * g + b]; U += h[(2 * (size_t)q + 1) * g + b]; }
+        *kinetic = K;
+        *potential = U;
+        return NB_OK;
+    }
     const double eps2 = (double)s->p.eps * (double)s->p.eps;
     with_layout(s, [&](auto L) {
         using real = typename decltype(L)::real;
@@ -2283,10 +2350,10 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
                  s->coll_large_n, (unsigned long long)s->coll_cap, resolve);
     const size_t len = strlen(buf);
     if (len < buflen) {
-        if (s->tree) snprintf(buf + len, buflen - len, " | force=tree theta=%.6g node_capacity=%llu depth_cap=%d%s%s", (double)s->p.theta,
+        if (s->tree) snprintf(buf + len, buflen - len, " | force=tree theta=%.6g node_capacity=%llu depth_cap=%d%s%s%s", (double)s->p.theta,
                               (unsigned long long)s->tree_cap, TREE_DEPTH_CAP,
                               !s->tree_leaves ? "" : tree_walk_is_group(s) ? " leaves=1 walk=group" : " leaves=1 walk=lane",
-                              s->tree_quad ? " quad=1" : "");
+                              s->tree_quad ? " quad=1" : "", s->tree_energy ? " energy=tree" : "");
         else snprintf(buf + len, buflen - len, " | force=direct");
     }
     return NB_OK;

@@ -20,6 +20,8 @@
 //                             NB_FLAG_TREE_QUADRUPOLE also the second moments about them (tree_com<true>, below)
 //   tree_walk                 Quadtree::acc per body, bodies in key order so that a wave's lanes walk neighbouring paths
 //   tree_integrate            kick_drift_one (nb_kernels.hip.h) unless the build failed
+// nb_energy of a NB_FLAG_TREE_ENERGY handle runs the build (bounds ... tree_com) and then tree_potential_group / _alone in place of
+// the walk: the potential over the nodes the wave-uniform walk takes, in fp64 (below).
 //
 // Pre-order layout from the sorted points.  Let L(u) be the number of leading levels points u and u + 1 share (-1 past
 // either end) and d(u) = max(L(u - 1), L(u)) + 1 the depth of point u's leaf.  Between leaf u - 1 and leaf u the traversal
@@ -548,6 +550,210 @@ void tree_walk_group(const float4 *__restrict__ nd, const uint32_t *__restrict__
         node = all_far && next > node ? next : node + 1u;    // (a leaf's next is node + 1)
     }
     acc[b] = make_float2(sx, sy);
+}
+
+// ---- potential energy -----------------------------------------------------------------------------------------------
+// nb_energy of a NB_FLAG_TREE_ENERGY handle: K = sum m v^2 / 2 and U = 1/2 sum m_i phi_i, phi_i summed over exactly the nodes the
+// wave-uniform force walk above takes for body i (the same float32 acceptance test without contraction, the same windows of 64
+// bodies in key order, the same tree_lane_alone rule), whatever the handle's rsqrt mode: the potential has this one walk
+// (tests/tree_energy_model.py is the CPU statement).  The node records, the moments and the positions are the float32 values
+// the build wrote; from the displacement on everything is float64: with d = c - body, R^2 = d^2 + eps^2
+//     a leaf, or an accepted cell without QUAD:   -m / R
+//     an accepted branch with QUAD:               -(m / R + 1.5 (d^T M d) / R^5 - 0.5 tr(M) / R^3)
+// (the potential whose gradient in d is the force term of tree_quad_term).  A term is taken where the force walk takes one:
+// d^2 > 0 in float32.  The body's own leaf therefore gives nothing, and the bodies that share its position are added one by one
+// from the sorted run of that position, -m_j / eps each (never "leaf mass - own mass": the leaf's float32 sum has lost the light
+// ones), so that every unordered pair counts once, as in energy_partials; with eps = 0 they are skipped and the result is finite.
+// A leaf that holds several bodies is the one node whose float32 mass is a rounded SUM, and at theta = 0 every other body sees it
+// as it stands: one rounding of 2^-24 there is 4e-10 of U on ic_random_333, above the 1e-10 the energy is held to against the direct
+// sum.  tree_leaf_residual therefore runs after the build: per point the float64 sum of its masses in the order of the run, and
+// lo[leaf] = (float)(that sum - the record's mass) into a per-node array of NB_FLAG_TREE_ENERGY handles (+4 B per node).  A leaf's
+// mass in a term is (double)record + (double)lo: the float64 sum to 2^-48, and the record itself for a leaf of one body (lo = 0).
+// Accepted branches keep the float32 mass of their record.  Empty leaves (mass 0) have no entry and none is read.
+// Massless bodies weigh nothing in K and U and do not walk.  Each kernel ends in the wave-shuffle and LDS reduction of
+// energy_partials: one (K, U) partial per block, summed on the host in block order.
+__device__ __forceinline__ double tree_potential_mono(float4 q, double m, float2 p, double eps2)
+{
+    const double dx = (double)q.x - (double)p.x, dy = (double)q.y - (double)p.y;
+    const double r2 = __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2));
+    return -m * rsqrt_f64(r2, 0.375);
+}
+
+// the mass of a node in a monopole term: a leaf with bodies adds its residual (above)
+__device__ __forceinline__ double tree_potential_mass(float4 q, bool leaf, uint32_t node, const float *__restrict__ lo)
+{
+    return leaf && q.z != 0.f ? (double)q.z + (double)lo[node] : (double)q.z;
+}
+
+// lo[leaf of point u] for every point (one thread per point; the leaf is the last node the point wrote, tree_emit)
+__global__ __launch_bounds__(256)
+void tree_leaf_residual(const float4 *__restrict__ nd, const uint64_t *__restrict__ base, const uint32_t *__restrict__ ufirst,
+                        const uint32_t *__restrict__ val, const float *__restrict__ mass, uint32_t n, const TreeStats *__restrict__ st,
+                        float *__restrict__ lo)
+{
+    const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= n || st->fail || u >= st->points) return;
+    const uint32_t leaf = (uint32_t)base[u + 1u] - 1u;
+    if (leaf >= (uint32_t)st->nodes) return;               // (never: tree_emit wrote it; the bound keeps a disagreement inside the array)
+    const uint32_t f = ufirst[u], e = u + 1u < st->points ? ufirst[u + 1u] : st->massive;
+    double m = (double)mass[val[f]];
+    for (uint32_t j = f + 1u; j < e; ++j) m += (double)mass[val[j]];
+    lo[leaf] = (float)(m - (double)nd[leaf].z);
+}
+
+__device__ __forceinline__ double tree_potential_quad(float4 q, float4 m, float2 p, double eps2)
+{
+    const double dx = (double)q.x - (double)p.x, dy = (double)q.y - (double)p.y;
+    const double r2 = __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2));
+    const double inv = rsqrt_f64(r2, 0.375);
+    const double inv2 = inv * inv, inv3 = inv2 * inv, inv5 = inv3 * inv2;
+    const double xx = (double)m.x, xy = (double)m.y, yy = (double)m.z;
+    const double rMr = dx * (xx * dx + xy * dy) + dy * (xy * dx + yy * dy);
+    return -((double)q.z * inv + 1.5 * rMr * inv5 - 0.5 * (xx + yy) * inv3);
+}
+
+// sum of -m_j / eps over the OTHER bodies of the sorted run that holds position i (i < massive)
+__device__ __forceinline__ double tree_potential_shared(uint32_t i, const uint32_t *__restrict__ val, const float *__restrict__ mass,
+                                                        const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
+                                                        const uint32_t *__restrict__ ufirst, const TreeStats *__restrict__ st, double eps2)
+{
+    if (!(eps2 > 0.0)) return 0.0;
+    const uint32_t u = (uint32_t)uidx[i] + head[i] - 1u;           // (uidx counts the key starts before i)
+    const uint32_t f = ufirst[u], e = u + 1u < st->points ? ufirst[u + 1u] : st->massive;
+    const double inv = rsqrt_f64(eps2, 0.375);
+    double s = 0.0;
+    for (uint32_t j = f; j < e; ++j)
+        if (j != i) s -= (double)mass[val[j]] * inv;
+    return s;
+}
+
+__device__ __forceinline__ void tree_energy_reduce(double k, double u, double *__restrict__ ksum, double *__restrict__ usum)
+{
+    __shared__ double red[2][4];
+    const uint32_t t = threadIdx.x;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        k += __shfl_down(k, off, 64);
+        u += __shfl_down(u, off, 64);
+    }
+    if ((t & 63u) == 0) { red[0][t >> 6] = k; red[1][t >> 6] = u; }
+    __syncthreads();
+    if (t == 0) {
+        double ks = 0.0, us = 0.0;
+        for (int w = 0; w < 4; ++w) { ks += red[0][w]; us += red[1][w]; }
+        ksum[blockIdx.x] = ks;
+        usum[blockIdx.x] = us;
+    }
+}
+
+__device__ __forceinline__ void tree_energy_of(uint32_t b, double phi, const float2 *__restrict__ vel, const float *__restrict__ mass,
+                                               double &k, double &u)
+{
+    const double m = (double)mass[b], vx = (double)vel[b].x, vy = (double)vel[b].y;
+    k = 0.5 * m * (vx * vx + vy * vy);
+    u = 0.5 * m * phi;
+}
+
+// the lanes tree_lane_alone takes out of their windows, massless ones excepted: the per-lane walk of tree_walk_one<.., true, QUAD>
+template <bool QUAD, typename... M>
+__global__ __launch_bounds__(256)
+void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
+                          const float2 *__restrict__ pos, const float2 *__restrict__ vel, const float *__restrict__ mass, uint32_t n,
+                          double eps2, float theta2, const TreeStats *__restrict__ st, const uint32_t *__restrict__ head,
+                          const uint64_t *__restrict__ uidx, const uint32_t *__restrict__ ufirst, double *__restrict__ ksum,
+                          double *__restrict__ usum, const float *__restrict__ lo, M... moments)
+{
+    static_assert(sizeof...(M) == (QUAD ? 1 : 0), "the moment array is the argument of the QUAD form alone");
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    double k = 0.0, u = 0.0;
+    if (i < n && !st->fail && i < st->massive && tree_lane_alone(i, head, uidx, ufirst, st)) {
+        const uint32_t b = val[i];
+        const float2 p = pos[b];
+        const uint32_t total = (uint32_t)st->nodes;
+        double phi = 0.0;
+        uint32_t node = 0;
+        while (node < total) {
+            const float4 q = nd[node];
+            const uint32_t next = nx[node];
+            float d2;
+            bool far;
+            {
+#pragma clang fp contract(off)
+                const float dx = q.x - p.x, dy = q.y - p.y;
+                d2 = dx * dx + dy * dy;
+                far = q.w < d2 * theta2;
+            }
+            const bool leaf = next == node + 1u;
+            if (far) {
+                if (d2 > 0.f) {
+                    if constexpr (QUAD) phi += leaf ? tree_potential_mono(q, tree_potential_mass(q, leaf, node, lo), p, eps2)
+                                                    : tree_potential_quad(q, tree_moments(moments...)[node], p, eps2);
+                    else phi += tree_potential_mono(q, tree_potential_mass(q, leaf, node, lo), p, eps2);
+                }
+                node = next > node ? next : node + 1u;
+            } else {
+                if (leaf && q.z != 0.f && d2 > 0.f) phi += tree_potential_mono(q, tree_potential_mass(q, leaf, node, lo), p, eps2);
+                node = node + 1u;
+            }
+        }
+        phi += tree_potential_shared(i, val, mass, head, uidx, ufirst, st, eps2);
+        tree_energy_of(b, phi, vel, mass, k, u);
+    }
+    tree_energy_reduce(k, u, ksum, usum);
+}
+
+// the windows: tree_walk_group's loop (node index through readfirstlane, one ballot, the moment record loaded inside the
+// wave-uniform accepted-branch path).  The lanes that take no part stay out of the loop, so they neither vote nor lead, and
+// join the block reduction with zeros.
+template <bool QUAD, typename... M>
+__global__ __launch_bounds__(256)
+void tree_potential_group(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
+                          const float2 *__restrict__ pos, const float2 *__restrict__ vel, const float *__restrict__ mass, uint32_t n,
+                          double eps2, float theta2, const TreeStats *__restrict__ st, const uint32_t *__restrict__ head,
+                          const uint64_t *__restrict__ uidx, const uint32_t *__restrict__ ufirst, double *__restrict__ ksum,
+                          double *__restrict__ usum, const float *__restrict__ lo, M... moments)
+{
+    static_assert(sizeof...(M) == (QUAD ? 1 : 0), "the moment array is the argument of the QUAD form alone");
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    double k = 0.0, u = 0.0;
+    if (i < n && !st->fail && !tree_lane_alone(i, head, uidx, ufirst, st)) {
+        const uint32_t b = val[i];
+        const float2 p = pos[b];
+        const uint32_t total = (uint32_t)st->nodes;
+        double phi = 0.0;
+        uint32_t node = 0;
+        while (node < total) {
+            node = (uint32_t)__builtin_amdgcn_readfirstlane((int)node);
+            const float4 q = nd[node];
+            const uint32_t next = nx[node];
+            float d2;
+            bool far;
+            {
+#pragma clang fp contract(off)
+                const float dx = q.x - p.x, dy = q.y - p.y;
+                d2 = dx * dx + dy * dy;
+                far = q.w < d2 * theta2;
+            }
+            const bool all_far = __ballot(!far) == 0ull;
+            const bool leaf = next == node + 1u;
+            if constexpr (QUAD) {
+                if (all_far && !leaf) {
+                    const float4 m = tree_moments(moments...)[node];
+                    if (d2 > 0.f) phi += tree_potential_quad(q, m, p, eps2);
+                } else if (leaf && (all_far || q.z != 0.f)) {
+                    const double m = tree_potential_mass(q, leaf, node, lo);       // (wave-uniform: one scalar load)
+                    if (d2 > 0.f) phi += tree_potential_mono(q, m, p, eps2);
+                }
+            } else if (all_far || (leaf && q.z != 0.f)) {
+                const double m = tree_potential_mass(q, leaf, node, lo);
+                if (d2 > 0.f) phi += tree_potential_mono(q, m, p, eps2);
+            }
+            node = all_far && next > node ? next : node + 1u;    // (a leaf's next is node + 1)
+        }
+        phi += tree_potential_shared(i, val, mass, head, uidx, ufirst, st, eps2);
+        tree_energy_of(b, phi, vel, mass, k, u);
+    }
+    tree_energy_reduce(k, u, ksum, usum);
 }
 
 // Kick and drift with acc[] as written by tree_walk.  A failed build integrates nothing: the positions are carried over.

@@ -14,6 +14,8 @@
  *                            so the result tends to the direct sum as theta -> 0; not the reference's arithmetic
  *              [-quad]       with -tree -leaves: accepted cells add their second moment (NB_FLAG_TREE_QUADRUPOLE): the same walk,
  *                            a smaller error at the same theta, +256 bytes per body
+ *              [-tree-energy] with -tree -leaves: the two energy readings walk the tree (NB_FLAG_TREE_ENERGY), O(n log n), where
+ *                            they otherwise sweep all n^2 / 2 pairs in fp64
  *              [-collide]    end every step with the reference's hard-sphere collisions (NB_EXTRA_COLLIDE, Simulation.hpp:216-346)
  *              [-shards P]   P sharded handles driven from this one process (device r mod #GPUs),
  *                            exchanged with nb_exchange_positions: multi-GPU without RCCL
@@ -104,6 +106,7 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(argv[i], "-leaves")) p.flags |= NB_FLAG_TREE_LEAVES;
         else if (!strcmp(argv[i], "-quad")) p.flags |= NB_FLAG_TREE_QUADRUPOLE;
+        else if (!strcmp(argv[i], "-tree-energy")) p.flags |= NB_FLAG_TREE_ENERGY;
         else if (!strcmp(argv[i], "-dump") && i + 1 < argc) dump = argv[++i];
         else if (!strcmp(argv[i], "-load") && i + 1 < argc) {
             /* the header's parameters become the defaults of this run; later options override them */

@@ -73,6 +73,7 @@ class Simulation:
         library=None,
         tree_leaves: bool = False,
         tree_quadrupole: bool = False,
+        tree_energy: bool = False,
     ):
         """The last arguments (from ``uniform_mass`` on) are ``nb_params.flags`` and the launch-geometry tuning fields
         (0 / True = the library's automatic choice); the library reads no environment variables.  ``mass_scaling``: False / None
@@ -84,13 +85,19 @@ class Simulation:
         (``force="tree"`` only, ValueError otherwise): the convergent tree force, NB_FLAG_TREE_LEAVES — leaves that are not accepted
         contribute, so the result tends to the direct sum as ``theta`` -> 0; not the reference's arithmetic.  ``tree_quadrupole``
         (``force="tree"`` with ``tree_leaves=True`` only, ValueError otherwise): accepted cells add their second moment,
-        NB_FLAG_TREE_QUADRUPOLE — the same walk, a smaller error at the same ``theta``, +256 bytes per body.  ``library``: another
+        NB_FLAG_TREE_QUADRUPOLE — the same walk, a smaller error at the same ``theta``, +256 bytes per body.  ``tree_energy``
+        (``force="tree"`` with ``tree_leaves=True`` only, ValueError otherwise): ``energy()`` walks the tree instead of sweeping all
+        pairs, NB_FLAG_TREE_ENERGY — O(n log n), the same pairs, the error of the force walk at this ``theta`` (``theta=0`` is the
+        direct energy); it rebuilds the tree and leaves the trajectory alone.  ``library``: another
         build of the library bound with ``_lib.bind`` (the tests' -DNB_TEST_HOOKS build); default the product."""
         if tree_leaves and force != "tree":
             raise ValueError('tree_leaves=True needs force="tree" (NB_FLAG_TREE_LEAVES selects a walk of the Barnes-Hut force)')
         if tree_quadrupole and not (force == "tree" and tree_leaves):
             raise ValueError('tree_quadrupole=True needs force="tree" and tree_leaves=True (NB_FLAG_TREE_QUADRUPOLE adds a term to the '
                              "accepted cells of the convergent Barnes-Hut force)")
+        if tree_energy and not (force == "tree" and tree_leaves):
+            raise ValueError('tree_energy=True needs force="tree" and tree_leaves=True (NB_FLAG_TREE_ENERGY makes energy() walk the tree '
+                             "of the convergent Barnes-Hut force)")
         lib = library if library is not None else L.load()
         if bodies.dtype not in (L.BODY_DTYPE, L.BODY3_DTYPE):
             raise TypeError("bodies must be a numpy array of nbodysim_amd.BODY_DTYPE (64-byte Body records)")
@@ -121,7 +128,7 @@ class Simulation:
                    | (L.NB_FLAG_MASS_SCALING_MEASURED if mass_scaling == "measured" else L.NB_FLAG_MASS_SCALING if mass_scaling is True
                       else L.NB_FLAG_NO_MASS_SCALING if mass_scaling is False else 0)
                    | (L.NB_FLAG_STATIC_ITEMS if static_items else 0) | (L.NB_FLAG_TREE_LEAVES if tree_leaves else 0)
-                   | (L.NB_FLAG_TREE_QUADRUPOLE if tree_quadrupole else 0))
+                   | (L.NB_FLAG_TREE_QUADRUPOLE if tree_quadrupole else 0) | (L.NB_FLAG_TREE_ENERGY if tree_energy else 0))
         p.sym_chunks_per_item, p.sym_aux_stream, p.sym_late_us, p.lanes_p = sym_chunks_per_item, sym_aux_stream, sym_late_us, lanes_p
         if sym_tail is not None:
             p.sym_tail[0], p.sym_tail[1], p.sym_tail[2] = sym_tail

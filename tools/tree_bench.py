@@ -19,6 +19,15 @@ last build, and direct / tree.
                                                equal-accuracy pairs (for each monopole theta the largest quadrupole theta whose
                                                median error is no worse)
 
+    python tools/tree_bench.py --energy [case ...]                  nb_energy on a convergent tree handle (theta 0.5, without and with the
+                                               quadrupole term): with NB_FLAG_TREE_ENERGY (the tree walk; cases 262144, 1048576 and
+                                               8388608 by default) and, up to 1 048 576 bodies, without it (the direct fp64 pair
+                                               sweep).  Every handle first steps for at least 2 s, then FIVE calls are timed (host
+                                               clock around the call, which waits for its result): one JSON line per (case, quad,
+                                               form) with the five figures, their median and spread (max - min), then per case the
+                                               ratio direct / tree.  Up to 1 048 576 bodies also |U_tree - U_direct| / |U_direct| of
+                                               the initial bodies at theta 1.0, 0.7, 0.5, 0.3, without and with the quadrupole term.
+
 With --theta the handle steps for at least 2 s, then FIVE stretches are timed; per stretch the milliseconds per step (host clock
 between two waits) and the milliseconds per walk (nb_profile_read, device events around the walk).  One JSON line per case: the
 five figures of each, their median and spread (max - min), and the walk nb_describe names.  With --leaves the line also carries
@@ -162,7 +171,57 @@ def sweep(cases, thetas=(1.0, 0.7, 0.5, 0.3)) -> None:
                               "step_ms_spread": [mono["step_ms_spread"], q["step_ms_spread"]]}), flush=True)
 
 
+def energy_calls(sim, dt: float, calls: int = 5) -> dict:
+    settle(sim, dt)
+    ms = []
+    for _ in range(calls):
+        sim.wait()
+        t0 = time.perf_counter()
+        k, u = sim.energy()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return {"energy_ms": [round(a, 4) for a in ms], "energy_ms_median": round(sorted(ms)[len(ms) // 2], 4),
+            "energy_ms_spread": round(max(ms) - min(ms), 4), "K": k, "U": u}
+
+
+def energy(cases, theta: float = 0.5, thetas=(1.0, 0.7, 0.5, 0.3)) -> None:
+    dt = 1e-3
+    for c in cases:
+        bodies = nb.plummer_2d(int(c), 42)
+        n = int(bodies.shape[0])
+        kw = dict(force="tree", rsqrt="exact", eps=0.01, device=0, tree_leaves=True)
+        if n <= 1 << 20:                                     # accuracy at the initial positions, before anything steps
+            with nb.Simulation(bodies, theta=theta, **kw) as sim:
+                u_direct = sim.energy()[1]
+            for t in thetas:
+                for quad in (False, True):
+                    with nb.Simulation(bodies, theta=t, tree_quadrupole=quad, tree_energy=True, **kw) as sim:
+                        u = sim.energy()[1]
+                    print(json.dumps({"case": c, "n": n, "theta": t, "quad": int(quad), "U_tree": u, "U_direct": u_direct,
+                                      "rel_err": float(f"{abs(u - u_direct) / abs(u_direct):.3e}")}), flush=True)
+        rows = {}
+        for quad in (False, True):
+            for flag in (True, False):
+                if not flag and n > 1 << 20:
+                    continue
+                with nb.Simulation(bodies, theta=theta, tree_quadrupole=quad, tree_energy=flag, **kw) as sim:
+                    row = {"case": c, "n": n, "theta": theta, "quad": int(quad), "energy": "tree" if flag else "direct"}
+                    row.update(energy_calls(sim, dt))
+                    if flag:
+                        row.update(sim.tree_stats())
+                rows[quad, flag] = row
+                print(json.dumps(row), flush=True)
+        for quad in (False, True):
+            if (quad, False) in rows:
+                t, d = rows[quad, True], rows[quad, False]
+                print(json.dumps({"case": c, "quad": int(quad), "direct_over_tree": round(d["energy_ms_median"] / t["energy_ms_median"], 2),
+                                  "energy_ms": [d["energy_ms_median"], t["energy_ms_median"]],
+                                  "energy_ms_spread": [d["energy_ms_spread"], t["energy_ms_spread"]]}), flush=True)
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--energy"]:
+        energy(sys.argv[2:] or ["262144", "1048576", "8388608"])
+        sys.exit(0)
     if sys.argv[1:2] == ["--trace"]:
         trace(sys.argv[2])
         sys.exit(0)
