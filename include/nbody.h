@@ -179,7 +179,7 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          NB_FLAG_SHARD_ALLREDUCE, the replicated one) with ONE rank — every pair is "local",
                                          the reduce-scatter / all-gather degenerate to copies.  For rehearsing the exchange
                                          path (nb_comm_*, nb_exchange_*) on a single GPU; never faster than a plain handle */
-       /* 2048 is unassigned (4096, 8192 and 16384 are the three tree bits below): nb_create rejects it like any unknown bit */
+       /* 2048 is unassigned (4096, 8192, 16384 and 32768 are the four tree bits below): nb_create rejects it like any unknown bit */
        NB_FLAG_TREE_LEAVES     = 4096,  /* NB_FORCE_TREE only (with NB_FORCE_DIRECT nb_create returns NB_EINVAL, naming the combination):
                                          the CONVERGENT Barnes-Hut force.  Cells, centres of mass, node order and the acceptance test
                                          size^2 < d^2 * theta^2 are those of NB_FORCE_TREE without the bit; a leaf that is not accepted adds
@@ -218,7 +218,7 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          per body of a tree handle, allocated only with the bit.  nb_describe appends " quad=1" after
                                          "walk=...".  Without the bit nothing changes: same bits, same launches, same memory.  Everything a
                                          NB_FLAG_TREE_LEAVES handle refuses or ignores it refuses or ignores with the bit too */
-       NB_FLAG_TREE_ENERGY = 16384 };   /* NB_FORCE_TREE with NB_FLAG_TREE_LEAVES only, with or without NB_FLAG_TREE_QUADRUPOLE (with
+       NB_FLAG_TREE_ENERGY = 16384,     /* NB_FORCE_TREE with NB_FLAG_TREE_LEAVES only, with or without NB_FLAG_TREE_QUADRUPOLE (with
                                          NB_FORCE_DIRECT or without NB_FLAG_TREE_LEAVES nb_create returns NB_EINVAL, naming the flag and the
                                          missing or conflicting partner; a walk without the leaves has no near field and no meaningful
                                          potential): nb_energy becomes an O(n log n) diagnostic.  It rebuilds the tree at the current
@@ -243,6 +243,34 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          *potential are not written.  nb_describe appends " energy=tree".  Without the bit nb_energy is
                                          unchanged on every kind of handle.  +64 bytes per body (the leaf residuals) and +16 bytes per 256
                                          bodies (the partials of the second launch) */
+       NB_FLAG_TREE_RELATIVE = 32768 }; /* NB_FORCE_TREE with NB_FLAG_TREE_LEAVES only, with or without NB_FLAG_TREE_QUADRUPOLE and
+                                         NB_FLAG_TREE_ENERGY (with NB_FORCE_DIRECT or without NB_FLAG_TREE_LEAVES nb_create returns NB_EINVAL,
+                                         naming the flag and the missing or conflicting partner): an opening test relative to the body's own
+                                         last acceleration, the criterion of GADGET-2, on top of the geometric one.  Per body i let (ax, ay)
+                                         be acc[i] AS THE HANDLE HOLDS IT: the acc field of the record after nb_create / nb_upload, the
+                                         result of the last successful force evaluation afterwards.  g_i = alpha * sqrt(ax ax + ay ay),
+                                         fp32, one rounding per operation, the square root correctly rounded, computed once before the walk.
+                                         A node {c, m, size^2} at d = c - body position is accepted ("far") for body i when BOTH hold
+                                             size^2 < d^2 * theta^2                            (the test of every tree handle: theta is the cap)
+                                             g_i == 0  ||  m * size^2 < (g_i * d^2) * d^2      (fp32, this order, no contraction)
+                                         i.e. G m size^2 / d^4 < alpha |a_prev| with G = 1.  alpha is set with nb_tree_alpha (below); at
+                                         creation it is 0.005, GADGET-2's customary setting, not a value measured for this library.
+                                         The relative walk opens whatever the theta walk opens and more: never coarser.  The group vote, the
+                                         windows of 64 in key order, the "walks alone" rule, the leaf terms, d^2 > 0 and the quadrupole term
+                                         are unchanged; the new test only feeds the vote.  With NB_RSQRT_QUAKE the per-lane walk runs
+                                         (tests/tree_rel_model.py restates it bit for bit).  CONSEQUENCES: fresh initial conditions (acc = 0)
+                                         make the first evaluation the plain theta walk, and every later one uses its predecessor; a caller
+                                         who wants the criterion active from step 1 calls nb_accelerations once before stepping (a second
+                                         call on fresh initial conditions already uses the first one's result).  A handle created from
+                                         nb_sync's records of a running handle, with first_frame set, continues that run bit for bit: a_prev
+                                         travels in the record.  A failed build leaves acc[], and so a_prev, untouched.  alpha = 0 switches
+                                         the test off: the bits of the same handle without the flag.  Deterministic as before: two handles
+                                         agree bit for bit, permuting the bodies (records included) permutes the bits.  With
+                                         NB_FLAG_TREE_ENERGY nb_energy walks with the same predicate and the acc[] of that moment: the nodes
+                                         a force evaluation issued now would take; it still touches nothing, and theta = 0 is still the
+                                         direct energy.  No memory is added.  nb_describe appends " alpha=<value>" after "walk=...", "quad=1"
+                                         and "energy=tree".  Without the bit nothing changes: same bits, same launches, same memory.
+                                         Everything a NB_FLAG_TREE_LEAVES handle refuses or ignores it refuses or ignores with the bit too */
 
 /* ---- parameters ----------------------------------------------------------- */
 typedef struct nb_params {
@@ -409,6 +437,12 @@ int nb_collision_stats(nb_sim *s, uint64_t *pairs_last_step, uint64_t *pairs_tot
  * evaluation and the evaluations that failed (node capacity, depth cap) since creation; any pointer may be NULL; NB_ESTATE
  * on a NB_FORCE_DIRECT handle. */
 int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, uint64_t *overflow_steps);
+
+/* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
+ * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without
+ * the flag.  At creation alpha is 0.005: GADGET-2's customary ErrTolForceAcc, not a number measured for this library.  A setter
+ * and not an nb_params field: sizeof(nb_params) and the ABI number stay. */
+int nb_tree_alpha(nb_sim *s, float alpha);
 
 /* Counters: Simulation::frame (Simulation.hpp:53) and sizes. */
 uint64_t nb_frame(const nb_sim *s);

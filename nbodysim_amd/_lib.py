@@ -36,6 +36,7 @@ NB_FLAG_MASS_SCALING_MEASURED = 1024
 NB_FLAG_TREE_LEAVES = 4096           # (2048 is unassigned)
 NB_FLAG_TREE_QUADRUPOLE = 8192       # with NB_FORCE_TREE and NB_FLAG_TREE_LEAVES only
 NB_FLAG_TREE_ENERGY = 16384          # with NB_FORCE_TREE and NB_FLAG_TREE_LEAVES only: nb_energy walks the tree
+NB_FLAG_TREE_RELATIVE = 32768        # with NB_FORCE_TREE and NB_FLAG_TREE_LEAVES only: acceleration-relative opening test (nb_tree_alpha)
 
 #: numpy view of the reference's 64-byte ``Body`` record (Body.hpp:6-13, Vec2.hpp:17-20)
 BODY_DTYPE = np.dtype(
@@ -172,6 +173,7 @@ PROTOTYPES = {
     "nb_collide_capacity": (C.c_int, [C.c_void_p, C.c_size_t]),
     "nb_collision_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "nb_tree_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "nb_tree_alpha": (C.c_int, [C.c_void_p, C.c_float]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),
     "nb_owned_begin": (C.c_size_t, [C.c_void_p]),

@@ -175,6 +175,8 @@ struct nb_sim {
     bool tree_leaves = false;                  // NB_FLAG_TREE_LEAVES: leaves that are not accepted contribute
     bool tree_quad = false;                    // NB_FLAG_TREE_QUADRUPOLE: accepted branches add their second moment
     bool tree_energy = false;                  // NB_FLAG_TREE_ENERGY: nb_energy walks the tree (ered_dev then holds 4 x ered_blocks)
+    bool tree_rel = false;                     // NB_FLAG_TREE_RELATIVE: the walks also test m size^2 < alpha |a_prev| d^4 (nb_tree_alpha)
+    float tree_alpha = 0.005f;                 // GADGET-2's customary setting; 0 switches the test off
     uint64_t tree_cap = 0;                     // node capacity: nodes allocated
     uint64_t tree_ovf_reported = 0;            // failed evaluations already reported by a synchronising call
     uint64_t *tree_k64[4] = {nullptr, nullptr, nullptr, nullptr};   // key words by body: high, low; two sort buffers
@@ -978,6 +980,10 @@ static int tree_alloc(nb_sim *s)
 // model restates bit for bit) with the Quake rsqrt.
 static bool tree_walk_is_group(const nb_sim *s) { return s->tree_leaves && s->p.rsqrt_mode != NB_RSQRT_QUAKE; }
 
+// NB_FLAG_TREE_RELATIVE with alpha != 0.  alpha = 0 switches the test off: the handle then runs the launches of the handle without
+// the flag, and so produces its bits.
+static bool tree_rel_active(const nb_sim *s) { return s->tree_rel && s->tree_alpha != 0.0f; }
+
 // The tree of pos[cur] (nb_tree.hip.h has the pipeline): bounds ... tree_com.  A force evaluation and, on a NB_FLAG_TREE_ENERGY
 // handle, nb_energy start with it.
 static int launch_tree_build(nb_sim *s)
@@ -1026,7 +1032,23 @@ static int launch_tree_force(nb_sim *s)
     if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
     const float eps2 = s->p.eps * s->p.eps;
     const float4 *qm = s->tree_qm;
-    if (tree_walk_is_group(s) && s->tree_quad) {     // the same two launches with the moment array (NB_FLAG_TREE_QUADRUPOLE)
+    if (tree_rel_active(s)) {               // NB_FLAG_TREE_RELATIVE: the same launches, a_prev = acc[] as it stands (nb_tree.hip.h, REL)
+        const float alpha = s->tree_alpha;
+        with_flags([&](auto quad) {
+            auto launch = [&](auto... tail) {
+                if (tree_walk_is_group(s)) {
+                    tree_walk_group<quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
+                                                                          s->tree_head, s->tree_uidx, s->tree_ufirst, tail...);
+                    tree_walk_alone<quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
+                                                                          s->tree_head, s->tree_uidx, s->tree_ufirst, tail...);
+                } else {
+                    tree_walk<RSQ_QUAKE, true, quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2,
+                                                                                     (float2 *)s->acc, st, tail...);
+                }
+            };
+            if constexpr (quad) launch(qm, alpha); else launch(alpha);
+        }, s->tree_quad);
+    } else if (tree_walk_is_group(s) && s->tree_quad) {     // the same two launches with the moment array (NB_FLAG_TREE_QUADRUPOLE)
         tree_walk_group<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
                                                         s->tree_head, s->tree_uidx, s->tree_ufirst, qm);
         tree_walk_alone<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
@@ -1066,7 +1088,20 @@ static int launch_tree_potential(nb_sim *s)
     const float4 *qm = s->tree_qm;
     const float *lo = s->tree_lo;
     tree_leaf_residual<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_base, s->tree_ufirst, v2, mass, n, st, s->tree_lo);
-    if (s->tree_quad) {
+    if (tree_rel_active(s)) {               // the predicate of a force evaluation issued now: acc[] of this moment, read only
+        const float2 *aprev = (const float2 *)s->acc;
+        const float alpha = s->tree_alpha;
+        with_flags([&](auto quad) {
+            auto launch = [&](auto... tail) {
+                tree_potential_group<quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st,
+                                                                           s->tree_head, s->tree_uidx, s->tree_ufirst, e, e + g, lo, tail...);
+                tree_potential_alone<quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st,
+                                                                           s->tree_head, s->tree_uidx, s->tree_ufirst, e + 2 * (size_t)g,
+                                                                           e + 3 * (size_t)g, lo, tail...);
+            };
+            if constexpr (quad) launch(qm, aprev, alpha); else launch(aprev, alpha);
+        }, s->tree_quad);
+    } else if (s->tree_quad) {
         tree_potential_group<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
                                                              s->tree_uidx, s->tree_ufirst, e, e + g, lo, qm);
         tree_potential_alone<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
@@ -1210,7 +1245,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
         nb_set_error("nb_create: quake rsqrt / sequential order are fp32 (reference arithmetic) modes");
         return nullptr;
     }
-    if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED | NB_FLAG_TREE_LEAVES | NB_FLAG_TREE_QUADRUPOLE | NB_FLAG_TREE_ENERGY)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
+    if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED | NB_FLAG_TREE_LEAVES | NB_FLAG_TREE_QUADRUPOLE | NB_FLAG_TREE_ENERGY | NB_FLAG_TREE_RELATIVE)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
     if (p.extras & ~(NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY | NB_EXTRA_COLLIDE)) { nb_set_error("nb_create: unknown bits in extras 0x%x", (unsigned)p.extras); return nullptr; }
     if (p.extras & NB_EXTRA_COLLIDE) {
         const char *why = p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
@@ -1222,6 +1257,13 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     }
     if (p.force != NB_FORCE_DIRECT && p.force != NB_FORCE_TREE) { nb_set_error("nb_create: bad force %d", p.force); return nullptr; }
     if (!(p.theta >= 0.0f) || !std::isfinite(p.theta)) { nb_set_error("nb_create: theta must be >= 0 and finite"); return nullptr; }
+    if ((p.flags & NB_FLAG_TREE_RELATIVE) && (p.force != NB_FORCE_TREE || !(p.flags & NB_FLAG_TREE_LEAVES))) {
+        nb_set_error("nb_create: NB_FLAG_TREE_RELATIVE %s: the flag adds an acceleration-relative opening test to the walks of the "
+                     "convergent Barnes-Hut force (NB_FORCE_TREE with NB_FLAG_TREE_LEAVES)",
+                     p.force == NB_FORCE_TREE ? "without NB_FLAG_TREE_LEAVES" : (p.flags & NB_FLAG_TREE_LEAVES) ? "with NB_FORCE_DIRECT"
+                                                : "with NB_FORCE_DIRECT and without NB_FLAG_TREE_LEAVES");
+        return nullptr;
+    }
     if ((p.flags & NB_FLAG_TREE_ENERGY) && (p.force != NB_FORCE_TREE || !(p.flags & NB_FLAG_TREE_LEAVES))) {
         nb_set_error("nb_create: NB_FLAG_TREE_ENERGY %s: the flag makes nb_energy walk the tree of the convergent Barnes-Hut force "
                      "(NB_FORCE_TREE with NB_FLAG_TREE_LEAVES; without the leaves a walk has no near field and no meaningful potential)",
@@ -1327,6 +1369,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     s->tree_leaves = s->tree && (p.flags & NB_FLAG_TREE_LEAVES) != 0;
     s->tree_quad = s->tree_leaves && (p.flags & NB_FLAG_TREE_QUADRUPOLE) != 0;
     s->tree_energy = s->tree_leaves && (p.flags & NB_FLAG_TREE_ENERGY) != 0;
+    s->tree_rel = s->tree_leaves && (p.flags & NB_FLAG_TREE_RELATIVE) != 0;
     if ((e = hipMalloc(&s->mass, n * s->rsz)) != hipSuccess) return fail("hipMalloc mass", e);
     if ((e = hipMalloc((void **)&s->radius, n * sizeof(float))) != hipSuccess) return fail("hipMalloc radius", e);
     if ((e = hipMalloc(&s->vel, s->i_count * r2)) != hipSuccess) return fail("hipMalloc vel", e);
@@ -2081,6 +2124,17 @@ extern "C" int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, ui
     return rc;
 }
 
+// alpha travels to the walks as a kernel argument: the evaluations enqueued so far keep theirs, the next one takes the new value
+extern "C" int nb_tree_alpha(nb_sim *s, float alpha)
+{
+    if (!s) return nb_fail(NB_EINVAL, "nb_tree_alpha: NULL handle");
+    if (!s->tree_rel) return nb_fail(NB_ESTATE, "nb_tree_alpha: the handle was created without NB_FLAG_TREE_RELATIVE");
+    if (!(alpha >= 0.0f) || std::isinf(alpha)) return nb_fail(NB_EINVAL, "nb_tree_alpha: alpha must be finite and >= 0 (got %g)", (double)alpha);
+    if (s->in_step) return nb_fail(NB_ESTATE, "nb_tree_alpha: a split step is in flight");
+    s->tree_alpha = alpha;
+    return NB_OK;
+}
+
 extern "C" uint64_t nb_frame(const nb_sim *s) { return s ? s->frame : 0; }
 extern "C" size_t nb_count(const nb_sim *s) { return s ? s->n : 0; }
 extern "C" size_t nb_owned_begin(const nb_sim *s) { return s ? s->i_begin : 0; }
@@ -2355,6 +2409,8 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
                               !s->tree_leaves ? "" : tree_walk_is_group(s) ? " leaves=1 walk=group" : " leaves=1 walk=lane",
                               s->tree_quad ? " quad=1" : "", s->tree_energy ? " energy=tree" : "");
         else snprintf(buf + len, buflen - len, " | force=direct");
+        const size_t len2 = strlen(buf);
+        if (s->tree_rel && len2 < buflen) snprintf(buf + len2, buflen - len2, " alpha=%.6g", (double)s->tree_alpha);
     }
     return NB_OK;
 }

@@ -18,7 +18,8 @@
 //   tree_emit                 writes the nodes: record {com.x, com.y, mass, size^2}, next (= index + subtree size), depth
 //   tree_com (per level)      centres of mass bottom-up, children 0..3 in order (Quadtree.hpp:236-258); with
 //                             NB_FLAG_TREE_QUADRUPOLE also the second moments about them (tree_com<true>, below)
-//   tree_walk                 Quadtree::acc per body, bodies in key order so that a wave's lanes walk neighbouring paths
+//   tree_walk                 Quadtree::acc per body, bodies in key order so that a wave's lanes walk neighbouring paths; with
+//                             NB_FLAG_TREE_RELATIVE the acceptance test also looks at the body's previous acceleration (REL, below)
 //   tree_integrate            kick_drift_one (nb_kernels.hip.h) unless the build failed
 // nb_energy of a NB_FLAG_TREE_ENERGY handle runs the build (bounds ... tree_com) and then tree_potential_group / _alone in place of
 // the walk: the potential over the nodes the wave-uniform walk takes, in fp64 (below).
@@ -314,6 +315,8 @@ void tree_emit(const uint64_t *__restrict__ uhi, const uint64_t *__restrict__ ul
 __device__ __forceinline__ float4 *tree_moments() { return nullptr; }
 __device__ __forceinline__ float4 *tree_moments(float4 *qm) { return qm; }
 __device__ __forceinline__ const float4 *tree_moments(const float4 *qm) { return qm; }
+template <typename... T>                                    // (the REL forms below: the moment array comes first, their own arguments after it)
+__device__ __forceinline__ const float4 *tree_moments(const float4 *qm, T...) { return qm; }
 
 template <bool QUAD, typename... M>
 __global__ __launch_bounds__(256)
@@ -373,6 +376,36 @@ void tree_com(float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const ui
 // (the second-order term of the softened potential about the centre of mass; the dipole vanishes there).  The record is loaded on
 // acceptance of a branch only; the nodes visited and the acceptance test are unchanged, and a leaf's term, accepted or not, is
 // the monopole term above, instruction for instruction.
+// REL (NB_FLAG_TREE_RELATIVE, with LEAVES; after the moment array, if any, the trailing arguments are then alpha — the walks — or
+// the acc[] array and alpha — the potential kernels): a node is accepted for a body when it passes the test above AND the
+// acceleration-relative one, m size^2 < (g d^2) d^2 with g = alpha |a_prev| of that body, i.e. G m size^2 / d^4 < alpha |a_prev|
+// with G = 1 (the opening criterion of GADGET-2).  a_prev is acc[] as the handle holds it: the walks read acc[b] once, before the
+// loop, in the thread that overwrites it at the end (no second array, no ordering problem); g is float32, one rounding per
+// operation, the square root correctly rounded (tests/tree_rel_model.py restates it with np.sqrt).  g == 0 (alpha = 0, or a body
+// whose acc is zero, as in fresh initial conditions) leaves the theta test alone.  theta stays the cap: the relative walk opens
+// whatever the theta walk opens and more, never less.  The vote, the windows, the terms and d^2 > 0 are unchanged: the test only
+// feeds the comparison that was there.  Every walk and potential kernel takes the new test from tree_far_rel.
+__device__ __forceinline__ bool tree_far_rel(float s2, float m, float d2, float g)
+{
+#pragma clang fp contract(off)
+    return (g == 0.f) | (m * s2 < (g * d2) * d2);
+}
+
+// g of a body from its previous acceleration.  (__builtin_sqrtf is the correctly rounded square root in device code: the
+// __fsqrt_rn intrinsic of this toolchain is the 1-ulp native one)
+__device__ __forceinline__ float tree_rel_g(float2 a, float alpha)
+{
+#pragma clang fp contract(off)
+    return alpha * __builtin_sqrtf(a.x * a.x + a.y * a.y);
+}
+
+__device__ __forceinline__ float tree_rel_alpha(float alpha) { return alpha; }
+__device__ __forceinline__ float tree_rel_alpha(const float4 *, float alpha) { return alpha; }
+__device__ __forceinline__ float tree_rel_alpha(const float2 *, float alpha) { return alpha; }
+__device__ __forceinline__ float tree_rel_alpha(const float4 *, const float2 *, float alpha) { return alpha; }
+__device__ __forceinline__ const float2 *tree_rel_aprev(const float2 *aprev, float) { return aprev; }
+__device__ __forceinline__ const float2 *tree_rel_aprev(const float4 *, const float2 *aprev, float) { return aprev; }
+
 template <int RSQ>
 __device__ __forceinline__ void tree_quad_term(float4 q, float4 m, float dx, float dy, float d2, float eps2, float &sx, float &sy)
 {
@@ -396,15 +429,18 @@ __device__ __forceinline__ void tree_quad_term(float4 q, float4 m, float dx, flo
     }
 }
 
-template <int RSQ, bool LEAVES, bool QUAD, typename... M>
+template <int RSQ, bool LEAVES, bool QUAD, bool REL, typename... M>
 __device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restrict__ nd, const uint32_t *__restrict__ nx,
                                               const uint32_t *__restrict__ val, const float2 *__restrict__ pos, float eps2, float theta2,
                                               float2 *__restrict__ acc, const TreeStats *__restrict__ st, M... moments)
 {
-    static_assert(sizeof...(M) == (QUAD ? 1 : 0) && (LEAVES || !QUAD), "the moment array is the argument of the QUAD form alone");
+    static_assert(sizeof...(M) == (QUAD ? 1 : 0) + (REL ? 1 : 0) && (LEAVES || !(QUAD || REL)),
+                  "the moment array is the argument of the QUAD form alone, alpha that of the REL form");
     const uint32_t b = val[i];
     const float2 p = pos[b];
     const uint32_t total = (uint32_t)st->nodes;
+    float g = 0.f;
+    if constexpr (REL) g = tree_rel_g(acc[b], tree_rel_alpha(moments...));
     float sx = 0.f, sy = 0.f;
     uint32_t node = 0;
     while (node < total) {
@@ -416,6 +452,7 @@ __device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restri
             dx = q.x - p.x; dy = q.y - p.y;
             d2 = dx * dx + dy * dy;
             far = q.w < d2 * theta2;
+            if constexpr (REL) far = far & tree_far_rel(q.w, q.z, d2, g);
         }
         auto term = [&]() {
             if constexpr (RSQ == RSQ_QUAKE) {
@@ -455,7 +492,7 @@ __device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restri
     acc[b] = make_float2(sx, sy);
 }
 
-template <int RSQ, bool LEAVES, bool QUAD, typename... M>
+template <int RSQ, bool LEAVES, bool QUAD, bool REL = false, typename... M>
 __global__ __launch_bounds__(256)
 void tree_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
@@ -463,7 +500,7 @@ void tree_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, c
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || st->fail) return;
-    tree_walk_one<RSQ, LEAVES, QUAD>(i, nd, nx, val, pos, eps2, theta2, acc, st, moments...);
+    tree_walk_one<RSQ, LEAVES, QUAD, REL>(i, nd, nx, val, pos, eps2, theta2, acc, st, moments...);
 }
 
 // The wave-uniform walk of NB_FLAG_TREE_LEAVES with NB_RSQRT_EXACT: one wave is one group, the 64 bodies at sorted positions
@@ -486,7 +523,7 @@ __device__ __forceinline__ bool tree_lane_alone(uint32_t i, const uint32_t *__re
     return (ufirst[(uint32_t)uidx[i] - 1u] >> 6) != (i >> 6);        // (not a head: at least one key starts before i)
 }
 
-template <bool QUAD, typename... M>
+template <bool QUAD, bool REL = false, typename... M>
 __global__ __launch_bounds__(256)
 void tree_walk_alone(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                      const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
@@ -495,22 +532,24 @@ void tree_walk_alone(const float4 *__restrict__ nd, const uint32_t *__restrict__
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || st->fail || !tree_lane_alone(i, head, uidx, ufirst, st)) return;
-    tree_walk_one<RSQ_EXACT, true, QUAD>(i, nd, nx, val, pos, eps2, theta2, acc, st, moments...);
+    tree_walk_one<RSQ_EXACT, true, QUAD, REL>(i, nd, nx, val, pos, eps2, theta2, acc, st, moments...);
 }
 
-template <bool QUAD, typename... M>
+template <bool QUAD, bool REL = false, typename... M>
 __global__ __launch_bounds__(256)
 void tree_walk_group(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                      const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
                      const TreeStats *__restrict__ st, const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
                      const uint32_t *__restrict__ ufirst, M... moments)
 {
-    static_assert(sizeof...(M) == (QUAD ? 1 : 0), "the moment array is the argument of the QUAD form alone");
+    static_assert(sizeof...(M) == (QUAD ? 1 : 0) + (REL ? 1 : 0), "the moment array is the argument of the QUAD form alone, alpha that of the REL form");
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || st->fail || tree_lane_alone(i, head, uidx, ufirst, st)) return;
     const uint32_t b = val[i];
     const float2 p = pos[b];
     const uint32_t total = (uint32_t)st->nodes;
+    float g = 0.f;
+    if constexpr (REL) g = tree_rel_g(acc[b], tree_rel_alpha(moments...));
     float sx = 0.f, sy = 0.f;
     uint32_t node = 0;
     while (node < total) {
@@ -524,6 +563,7 @@ void tree_walk_group(const float4 *__restrict__ nd, const uint32_t *__restrict__
             dx = q.x - p.x; dy = q.y - p.y;
             d2 = dx * dx + dy * dy;
             far = q.w < d2 * theta2;
+            if constexpr (REL) far = far & tree_far_rel(q.w, q.z, d2, g);
         }
         const bool all_far = __ballot(!far) == 0ull;
         const bool leaf = next == node + 1u;
@@ -655,7 +695,7 @@ __device__ __forceinline__ void tree_energy_of(uint32_t b, double phi, const flo
 }
 
 // the lanes tree_lane_alone takes out of their windows, massless ones excepted: the per-lane walk of tree_walk_one<.., true, QUAD>
-template <bool QUAD, typename... M>
+template <bool QUAD, bool REL = false, typename... M>
 __global__ __launch_bounds__(256)
 void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                           const float2 *__restrict__ pos, const float2 *__restrict__ vel, const float *__restrict__ mass, uint32_t n,
@@ -663,13 +703,15 @@ void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restr
                           const uint64_t *__restrict__ uidx, const uint32_t *__restrict__ ufirst, double *__restrict__ ksum,
                           double *__restrict__ usum, const float *__restrict__ lo, M... moments)
 {
-    static_assert(sizeof...(M) == (QUAD ? 1 : 0), "the moment array is the argument of the QUAD form alone");
+    static_assert(sizeof...(M) == (QUAD ? 1 : 0) + (REL ? 2 : 0), "the moment array is the argument of the QUAD form alone, acc[] and alpha those of the REL form");
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     double k = 0.0, u = 0.0;
     if (i < n && !st->fail && i < st->massive && tree_lane_alone(i, head, uidx, ufirst, st)) {
         const uint32_t b = val[i];
         const float2 p = pos[b];
         const uint32_t total = (uint32_t)st->nodes;
+        float g = 0.f;
+        if constexpr (REL) g = tree_rel_g(tree_rel_aprev(moments...)[b], tree_rel_alpha(moments...));
         double phi = 0.0;
         uint32_t node = 0;
         while (node < total) {
@@ -682,6 +724,7 @@ void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restr
                 const float dx = q.x - p.x, dy = q.y - p.y;
                 d2 = dx * dx + dy * dy;
                 far = q.w < d2 * theta2;
+                if constexpr (REL) far = far & tree_far_rel(q.w, q.z, d2, g);
             }
             const bool leaf = next == node + 1u;
             if (far) {
@@ -705,7 +748,7 @@ void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restr
 // the windows: tree_walk_group's loop (node index through readfirstlane, one ballot, the moment record loaded inside the
 // wave-uniform accepted-branch path).  The lanes that take no part stay out of the loop, so they neither vote nor lead, and
 // join the block reduction with zeros.
-template <bool QUAD, typename... M>
+template <bool QUAD, bool REL = false, typename... M>
 __global__ __launch_bounds__(256)
 void tree_potential_group(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                           const float2 *__restrict__ pos, const float2 *__restrict__ vel, const float *__restrict__ mass, uint32_t n,
@@ -713,13 +756,15 @@ void tree_potential_group(const float4 *__restrict__ nd, const uint32_t *__restr
                           const uint64_t *__restrict__ uidx, const uint32_t *__restrict__ ufirst, double *__restrict__ ksum,
                           double *__restrict__ usum, const float *__restrict__ lo, M... moments)
 {
-    static_assert(sizeof...(M) == (QUAD ? 1 : 0), "the moment array is the argument of the QUAD form alone");
+    static_assert(sizeof...(M) == (QUAD ? 1 : 0) + (REL ? 2 : 0), "the moment array is the argument of the QUAD form alone, acc[] and alpha those of the REL form");
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     double k = 0.0, u = 0.0;
     if (i < n && !st->fail && !tree_lane_alone(i, head, uidx, ufirst, st)) {
         const uint32_t b = val[i];
         const float2 p = pos[b];
         const uint32_t total = (uint32_t)st->nodes;
+        float g = 0.f;
+        if constexpr (REL) g = tree_rel_g(tree_rel_aprev(moments...)[b], tree_rel_alpha(moments...));
         double phi = 0.0;
         uint32_t node = 0;
         while (node < total) {
@@ -733,6 +778,7 @@ void tree_potential_group(const float4 *__restrict__ nd, const uint32_t *__restr
                 const float dx = q.x - p.x, dy = q.y - p.y;
                 d2 = dx * dx + dy * dy;
                 far = q.w < d2 * theta2;
+                if constexpr (REL) far = far & tree_far_rel(q.w, q.z, d2, g);
             }
             const bool all_far = __ballot(!far) == 0ull;
             const bool leaf = next == node + 1u;

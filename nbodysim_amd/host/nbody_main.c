@@ -16,6 +16,8 @@
  *                            a smaller error at the same theta, +256 bytes per body
  *              [-tree-energy] with -tree -leaves: the two energy readings walk the tree (NB_FLAG_TREE_ENERGY), O(n log n), where
  *                            they otherwise sweep all n^2 / 2 pairs in fp64
+ *              [-alpha A]    with -tree -leaves: the acceleration-relative opening test (NB_FLAG_TREE_RELATIVE, nb_tree_alpha): a cell
+ *                            is accepted only if m size^2 / d^4 < A |a_prev| as well; theta stays the cap
  *              [-collide]    end every step with the reference's hard-sphere collisions (NB_EXTRA_COLLIDE, Simulation.hpp:216-346)
  *              [-shards P]   P sharded handles driven from this one process (device r mod #GPUs),
  *                            exchanged with nb_exchange_positions: multi-GPU without RCCL
@@ -76,7 +78,8 @@ int main(int argc, char **argv)
     size_t n = 65536;
     uint64_t frame0 = 0;
     int steps = 20, sync_every = 0, shards = 1, reference_ics = 0, n_given = 0, rccl = 0, shards_given = 0;
-    int rank = -1, world = 0, device = -1, deadline_s = 120;
+    int rank = -1, world = 0, device = -1, deadline_s = 120, alpha_given = 0;
+    float alpha = 0.0f;
     unsigned long long nonce = 0;
     const char *idfile = NULL;
     unsigned seed = 42;
@@ -107,6 +110,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-leaves")) p.flags |= NB_FLAG_TREE_LEAVES;
         else if (!strcmp(argv[i], "-quad")) p.flags |= NB_FLAG_TREE_QUADRUPOLE;
         else if (!strcmp(argv[i], "-tree-energy")) p.flags |= NB_FLAG_TREE_ENERGY;
+        else if (!strcmp(argv[i], "-alpha") && i + 1 < argc) { p.flags |= NB_FLAG_TREE_RELATIVE; alpha = (float)atof(argv[++i]); alpha_given = 1; }
         else if (!strcmp(argv[i], "-dump") && i + 1 < argc) dump = argv[++i];
         else if (!strcmp(argv[i], "-load") && i + 1 < argc) {
             /* the header's parameters become the defaults of this run; later options override them */
@@ -273,6 +277,7 @@ int main(int argc, char **argv)
     }
     nb_sim *sim = nb_create(bodies, n, &p);
     if (!sim) DIE("nb_create: %s", nb_last_error());
+    if (alpha_given) CHECK(nb_tree_alpha(sim, alpha));
     char desc[1024];
     CHECK(nb_describe(sim, desc, sizeof desc));
     printf("%s\n", desc);

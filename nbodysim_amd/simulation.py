@@ -74,6 +74,7 @@ class Simulation:
         tree_leaves: bool = False,
         tree_quadrupole: bool = False,
         tree_energy: bool = False,
+        tree_alpha: Optional[float] = None,
     ):
         """The last arguments (from ``uniform_mass`` on) are ``nb_params.flags`` and the launch-geometry tuning fields
         (0 / True = the library's automatic choice); the library reads no environment variables.  ``mass_scaling``: False / None
@@ -88,7 +89,11 @@ class Simulation:
         NB_FLAG_TREE_QUADRUPOLE — the same walk, a smaller error at the same ``theta``, +256 bytes per body.  ``tree_energy``
         (``force="tree"`` with ``tree_leaves=True`` only, ValueError otherwise): ``energy()`` walks the tree instead of sweeping all
         pairs, NB_FLAG_TREE_ENERGY — O(n log n), the same pairs, the error of the force walk at this ``theta`` (``theta=0`` is the
-        direct energy); it rebuilds the tree and leaves the trajectory alone.  ``library``: another
+        direct energy); it rebuilds the tree and leaves the trajectory alone.  ``tree_alpha`` (None or a float; ``force="tree"`` with
+        ``tree_leaves=True`` only, ValueError otherwise): NB_FLAG_TREE_RELATIVE — a cell is accepted only if it also passes
+        m size^2 / d^4 < ``tree_alpha`` |a_prev| with the body's own last acceleration (``theta`` stays the cap; fresh initial
+        conditions have a_prev = 0, so call ``accelerations()`` once before stepping to have the test active from step 1);
+        ``set_tree_alpha`` changes it between steps, 0 switches it off.  ``library``: another
         build of the library bound with ``_lib.bind`` (the tests' -DNB_TEST_HOOKS build); default the product."""
         if tree_leaves and force != "tree":
             raise ValueError('tree_leaves=True needs force="tree" (NB_FLAG_TREE_LEAVES selects a walk of the Barnes-Hut force)')
@@ -98,6 +103,9 @@ class Simulation:
         if tree_energy and not (force == "tree" and tree_leaves):
             raise ValueError('tree_energy=True needs force="tree" and tree_leaves=True (NB_FLAG_TREE_ENERGY makes energy() walk the tree '
                              "of the convergent Barnes-Hut force)")
+        if tree_alpha is not None and not (force == "tree" and tree_leaves):
+            raise ValueError('tree_alpha needs force="tree" and tree_leaves=True (NB_FLAG_TREE_RELATIVE adds an acceleration-relative '
+                             "opening test to the walks of the convergent Barnes-Hut force)")
         lib = library if library is not None else L.load()
         if bodies.dtype not in (L.BODY_DTYPE, L.BODY3_DTYPE):
             raise TypeError("bodies must be a numpy array of nbodysim_amd.BODY_DTYPE (64-byte Body records)")
@@ -128,7 +136,8 @@ class Simulation:
                    | (L.NB_FLAG_MASS_SCALING_MEASURED if mass_scaling == "measured" else L.NB_FLAG_MASS_SCALING if mass_scaling is True
                       else L.NB_FLAG_NO_MASS_SCALING if mass_scaling is False else 0)
                    | (L.NB_FLAG_STATIC_ITEMS if static_items else 0) | (L.NB_FLAG_TREE_LEAVES if tree_leaves else 0)
-                   | (L.NB_FLAG_TREE_QUADRUPOLE if tree_quadrupole else 0) | (L.NB_FLAG_TREE_ENERGY if tree_energy else 0))
+                   | (L.NB_FLAG_TREE_QUADRUPOLE if tree_quadrupole else 0) | (L.NB_FLAG_TREE_ENERGY if tree_energy else 0)
+                   | (L.NB_FLAG_TREE_RELATIVE if tree_alpha is not None else 0))
         p.sym_chunks_per_item, p.sym_aux_stream, p.sym_late_us, p.lanes_p = sym_chunks_per_item, sym_aux_stream, sym_late_us, lanes_p
         if sym_tail is not None:
             p.sym_tail[0], p.sym_tail[1], p.sym_tail[2] = sym_tail
@@ -146,6 +155,13 @@ class Simulation:
         self._h = lib.nb_create(bodies.ctypes.data, bodies.shape[0], C.byref(p))
         if not self._h:
             raise L.NBodyError("nb_create", L.last_error_code(lib), L.last_error(lib))
+        if tree_alpha is not None:
+            rc = lib.nb_tree_alpha(self._h, tree_alpha)
+            if rc:
+                err = L.NBodyError("nb_tree_alpha", L.last_error_code(lib), L.last_error(lib))
+                lib.nb_destroy(self._h)
+                self._h = None
+                raise err
         self.n = int(lib.nb_count(self._h))
         self.i_begin = int(lib.nb_owned_begin(self._h))
         self.i_count = int(lib.nb_owned_count(self._h))
@@ -233,6 +249,10 @@ class Simulation:
         depth = C.c_uint32()
         L.check("nb_tree_stats", self._lib.nb_tree_stats(self._h, C.byref(nodes), C.byref(depth), C.byref(ovf)), self._lib)
         return {"nodes": int(nodes.value), "max_depth": int(depth.value), "overflow_steps": int(ovf.value)}
+
+    def set_tree_alpha(self, alpha: float) -> None:
+        """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
+        L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)
 
     def dump(self, path: str) -> None:
         L.check("nb_dump", self._lib.nb_dump(self._h, str(path).encode()), self._lib)

@@ -19,6 +19,13 @@ last build, and direct / tree.
                                                equal-accuracy pairs (for each monopole theta the largest quadrupole theta whose
                                                median error is no worse)
 
+    python tools/tree_bench.py --theta T --leaves [--quad] --alpha A [case ...]   the same with the acceleration-relative opening test
+                                               (NB_FLAG_TREE_RELATIVE, nb_tree_alpha): theta is the cap, A is alpha
+    python tools/tree_bench.py --sweep --alpha [case ...]           the theta rows of --sweep and, under theta = 1, alpha 0.02, 0.005, 0.0025,
+                                               0.001, each without and with the quadrupole term; then per (case, quad) and theta the
+                                               largest alpha whose 99th-percentile error is no worse than that theta's, with both
+                                               walk and step times and their spreads side by side
+
     python tools/tree_bench.py --energy [case ...]                  nb_energy on a convergent tree handle (theta 0.5, without and with the
                                                quadrupole term): with NB_FLAG_TREE_ENERGY (the tree walk; cases 262144, 1048576 and
                                                8388608 by default) and, up to 1 048 576 bodies, without it (the direct fp64 pair
@@ -31,8 +38,9 @@ last build, and direct / tree.
 With --theta the handle steps for at least 2 s, then FIVE stretches are timed; per stretch the milliseconds per step (host clock
 between two waits) and the milliseconds per walk (nb_profile_read, device events around the walk).  One JSON line per case: the
 five figures of each, their median and spread (max - min), and the walk nb_describe names.  With --leaves the line also carries
-the median and the 99th percentile of the per-body error of the INITIAL accelerations, |a - a_direct| / |a_direct|, against a
-direct-sum handle (hardware rsqrt) on the same bodies.  A library built from another commit is measured through NBODY_HIP_LIB
+the median, the 99th percentile and the maximum of the per-body error of the INITIAL accelerations, |a - a_direct| / |a_direct|,
+against a direct-sum handle (hardware rsqrt) on the same bodies; with --alpha it is the error of the SECOND evaluation there
+(fresh bodies have no previous acceleration: the first evaluation is the plain theta walk and the second one uses its result).  A library built from another commit is measured through NBODY_HIP_LIB
 (the cases without --leaves need nothing this tool adds).
 """
 from __future__ import annotations
@@ -78,20 +86,28 @@ def direct_accelerations(case: str):
         return sim.accelerations().astype("float64")
 
 
-def run_walk(case: str, theta: float, leaves: bool, stretches: int = 5, timed_s: float = 1.0, quad: bool = False, direct=None) -> dict:
+def run_walk(case: str, theta: float, leaves: bool, stretches: int = 5, timed_s: float = 1.0, quad: bool = False, direct=None,
+             alpha=None) -> dict:
     bodies, dt = nb.plummer_2d(int(case), 42), 1e-3
     kw = dict(tree_leaves=True) if leaves else {}
     if quad:
         kw["tree_quadrupole"] = True
+    if alpha is not None:
+        kw["tree_alpha"] = alpha
     with nb.Simulation(bodies, force="tree", rsqrt="exact", theta=theta, eps=0.01, device=0, **kw) as sim:
         d = sim.describe()
         out = {"case": case, "n": int(bodies.shape[0]), "theta": theta, "leaves": int(leaves), "quad": int(quad),
                "walk": d.split(" walk=")[1].split()[0] if " walk=" in d else "lane"}
+        if alpha is not None:
+            out["alpha"] = alpha
         if direct is not None:
+            if alpha is not None:
+                sim.accelerations()                          # (the criterion is active from the second evaluation on)
             a = sim.accelerations().astype("float64")
             mag = (direct[:, 0] ** 2 + direct[:, 1] ** 2) ** 0.5
             err = sorted(((a[:, 0] - direct[:, 0]) ** 2 + (a[:, 1] - direct[:, 1]) ** 2) ** 0.5 / mag)
             out["err_median"], out["err_p99"] = float(f"{err[len(err) // 2]:.3e}"), float(f"{err[len(err) * 99 // 100]:.3e}")
+            out["err_max"] = float(f"{err[-1]:.3e}")
         est = settle(sim, dt)
         k = max(3, min(int(timed_s / est), 5000))
         step_ms, walk_ms = [], []
@@ -150,7 +166,7 @@ def trace(case: str, steps: int = 50) -> None:
     print(json.dumps({"case": case, "traced_steps": steps}))
 
 
-def sweep(cases, thetas=(1.0, 0.7, 0.5, 0.3)) -> None:
+def sweep(cases, thetas=(1.0, 0.7, 0.5, 0.3), alphas=()) -> None:
     for c in cases:
         direct = direct_accelerations(c)
         rows = {}
@@ -158,6 +174,24 @@ def sweep(cases, thetas=(1.0, 0.7, 0.5, 0.3)) -> None:
             for quad in (False, True):
                 rows[theta, quad] = run_walk(c, theta, True, quad=quad, direct=direct)
                 print(json.dumps(rows[theta, quad]), flush=True)
+        rel = {}
+        for alpha in alphas:                                 # the relative criterion under the theta = 1 cap
+            for quad in (False, True):
+                rel[alpha, quad] = run_walk(c, 1.0, True, quad=quad, direct=direct, alpha=alpha)
+                print(json.dumps(rel[alpha, quad]), flush=True)
+        for quad in (False, True) if alphas else ():         # equal tail: the largest alpha whose 99th percentile is no worse
+            for theta in thetas:
+                base = rows[theta, quad]
+                ok = [a for a in alphas if rel[a, quad]["err_p99"] <= base["err_p99"]]
+                if not ok:
+                    print(json.dumps({"case": c, "quad": int(quad), "equal_tail": {"theta": theta, "alpha": None}}), flush=True)
+                    continue
+                r = rel[max(ok), quad]
+                print(json.dumps({"case": c, "quad": int(quad), "equal_tail": {"theta": theta, "alpha": max(ok)},
+                                  "err_p99": [base["err_p99"], r["err_p99"]], "err_max": [base["err_max"], r["err_max"]],
+                                  "walk_ms": [base["walk_ms_median"], r["walk_ms_median"]], "step_ms": [base["step_ms_median"], r["step_ms_median"]],
+                                  "walk_ms_spread": [base["walk_ms_spread"], r["walk_ms_spread"]],
+                                  "step_ms_spread": [base["step_ms_spread"], r["step_ms_spread"]]}), flush=True)
         for theta in thetas:                                 # equal accuracy: the largest quadrupole theta that is no worse
             mono = rows[theta, False]
             ok = [t for t in thetas if rows[t, True]["err_median"] <= mono["err_median"]]
@@ -226,18 +260,26 @@ if __name__ == "__main__":
         trace(sys.argv[2])
         sys.exit(0)
     if sys.argv[1:2] == ["--sweep"]:
-        sweep(sys.argv[2:] or ["262144", "1048576"])
+        args = sys.argv[2:]
+        relative = "--alpha" in args
+        if relative:
+            args.remove("--alpha")
+        sweep(args or ["262144", "1048576"], alphas=(0.02, 0.005, 0.0025, 0.001) if relative else ())
         sys.exit(0)
     if "--theta" in sys.argv:
         args = sys.argv[1:]
         theta = float(args.pop(args.index("--theta") + 1))
         args.remove("--theta")
+        alpha = None
+        if "--alpha" in args:
+            alpha = float(args.pop(args.index("--alpha") + 1))
+            args.remove("--alpha")
         leaves, quad = "--leaves" in args, "--quad" in args
         for flag in ("--leaves", "--quad"):
             if flag in args:
                 args.remove(flag)
         for c in args or ["262144", "1048576"]:
-            print(json.dumps(run_walk(c, theta, leaves, quad=quad, direct=direct_accelerations(c) if leaves else None)), flush=True)
+            print(json.dumps(run_walk(c, theta, leaves, quad=quad, direct=direct_accelerations(c) if leaves else None, alpha=alpha)), flush=True)
         sys.exit(0)
     for c in sys.argv[1:] or ["default", "262144", "1048576", "8388608"]:
         print(json.dumps(run(c)), flush=True)
