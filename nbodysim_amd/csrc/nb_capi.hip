@@ -1012,10 +1012,10 @@ static int launch_tree_build(nb_sim *s)
     tree_emit<<<g2, 256, 0, s->stream>>>(s->tree_uhi, s->tree_ulo, s->tree_ufirst, v2, pos, mass, s->tree_base, n, s->tree_root_dev, s->tree_cap,
                                          s->tree_nd, s->tree_nx, s->tree_dp, st, s->frame);
     const uint32_t gc = (uint32_t)std::min<uint64_t>((s->tree_cap + 255u) / 256u, 8u * (uint32_t)s->cus);
-    for (int level = TREE_DEPTH_CAP - 1; level >= 0; --level) {
-        if (s->tree_quad) tree_com<true><<<gc, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, (uint32_t)level, st, s->tree_qm);
-        else tree_com<false><<<gc, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, (uint32_t)level, st);
-    }
+    with_flags([&](auto quad) {
+        for (int level = TREE_DEPTH_CAP - 1; level >= 0; --level)
+            tree_com<quad><<<gc, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, (uint32_t)level, st, s->tree_qm);
+    }, s->tree_quad);
     HIPCHK(hipGetLastError());
     return NB_OK;
 }
@@ -1030,41 +1030,27 @@ static int launch_tree_force(nb_sim *s)
     TreeStats *st = s->tree_stats;
     std::pair<hipEvent_t, hipEvent_t> pr;
     if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
-    const float eps2 = s->p.eps * s->p.eps;
+    const float eps2 = s->p.eps * s->p.eps, alpha = s->tree_alpha;
     const float4 *qm = s->tree_qm;
-    if (tree_rel_active(s)) {               // NB_FLAG_TREE_RELATIVE: the same launches, a_prev = acc[] as it stands (nb_tree.hip.h, REL)
-        const float alpha = s->tree_alpha;
-        with_flags([&](auto quad) {
-            auto launch = [&](auto... tail) {
-                if (tree_walk_is_group(s)) {
-                    tree_walk_group<quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
-                                                                          s->tree_head, s->tree_uidx, s->tree_ufirst, tail...);
-                    tree_walk_alone<quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
-                                                                          s->tree_head, s->tree_uidx, s->tree_ufirst, tail...);
-                } else {
-                    tree_walk<RSQ_QUAKE, true, quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2,
-                                                                                     (float2 *)s->acc, st, tail...);
-                }
-            };
-            if constexpr (quad) launch(qm, alpha); else launch(alpha);
-        }, s->tree_quad);
-    } else if (tree_walk_is_group(s) && s->tree_quad) {     // the same two launches with the moment array (NB_FLAG_TREE_QUADRUPOLE)
-        tree_walk_group<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
-                                                        s->tree_head, s->tree_uidx, s->tree_ufirst, qm);
-        tree_walk_alone<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
-                                                        s->tree_head, s->tree_uidx, s->tree_ufirst, qm);
-    } else if (tree_walk_is_group(s)) {     // the group walk, then the few lanes that left it (nb_tree.hip.h): one "force kernel" interval
-        tree_walk_group<false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
-                                                         s->tree_head, s->tree_uidx, s->tree_ufirst);
-        tree_walk_alone<false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
-                                                         s->tree_head, s->tree_uidx, s->tree_ufirst);
-    } else if (s->tree_quad) {              // (with NB_FLAG_TREE_LEAVES only, and here with the Quake rsqrt: nb_create)
-        tree_walk<RSQ_QUAKE, true, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st, qm);
-    } else {
-        with_flags([&](auto q, auto leaves) {
-            tree_walk<q ? RSQ_QUAKE : RSQ_EXACT, leaves, false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2,
-                                                                                            (float2 *)s->acc, st);
-        }, s->p.rsqrt_mode == NB_RSQRT_QUAKE, s->tree_leaves);
+    const bool quake = s->p.rsqrt_mode == NB_RSQRT_QUAKE;
+    auto lanes = [&](auto kernel) {         // a per-lane walk
+        kernel<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st, qm, alpha);
+    };
+    auto windows = [&](auto kernel) {       // tree_walk_group and tree_walk_alone: the same with the three arrays of tree_lane_alone
+        kernel<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
+                                         s->tree_head, s->tree_uidx, s->tree_ufirst, qm, alpha);
+    };
+    if (tree_walk_is_group(s)) {            // the group walk, then the few lanes that left it (nb_tree.hip.h): one "force kernel" interval
+        with_flags([&](auto quad, auto rel) {
+            windows(tree_walk_group<quad, rel>);
+            windows(tree_walk_alone<quad, rel>);
+        }, s->tree_quad, tree_rel_active(s));
+    } else if (s->tree_leaves) {            // per lane (the Quake rsqrt: tree_walk_is_group): QUAD and REL exist with RSQ_QUAKE only
+        with_flags([&](auto q, auto quad, auto rel) {
+            if constexpr (q || !(quad || rel)) lanes(tree_walk<q ? RSQ_QUAKE : RSQ_EXACT, true, quad, rel>);
+        }, quake, s->tree_quad, tree_rel_active(s));
+    } else {                                // the reference's walk
+        with_flags([&](auto q) { lanes(tree_walk<q ? RSQ_QUAKE : RSQ_EXACT, false, false, false>); }, quake);
     }
     HIPCHK(hipGetLastError());
     if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
@@ -1088,30 +1074,14 @@ static int launch_tree_potential(nb_sim *s)
     const float4 *qm = s->tree_qm;
     const float *lo = s->tree_lo;
     tree_leaf_residual<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_base, s->tree_ufirst, v2, mass, n, st, s->tree_lo);
-    if (tree_rel_active(s)) {               // the predicate of a force evaluation issued now: acc[] of this moment, read only
-        const float2 *aprev = (const float2 *)s->acc;
-        const float alpha = s->tree_alpha;
-        with_flags([&](auto quad) {
-            auto launch = [&](auto... tail) {
-                tree_potential_group<quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st,
-                                                                           s->tree_head, s->tree_uidx, s->tree_ufirst, e, e + g, lo, tail...);
-                tree_potential_alone<quad, true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st,
-                                                                           s->tree_head, s->tree_uidx, s->tree_ufirst, e + 2 * (size_t)g,
-                                                                           e + 3 * (size_t)g, lo, tail...);
-            };
-            if constexpr (quad) launch(qm, aprev, alpha); else launch(aprev, alpha);
-        }, s->tree_quad);
-    } else if (s->tree_quad) {
-        tree_potential_group<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
-                                                             s->tree_uidx, s->tree_ufirst, e, e + g, lo, qm);
-        tree_potential_alone<true><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
-                                                             s->tree_uidx, s->tree_ufirst, e + 2 * (size_t)g, e + 3 * (size_t)g, lo, qm);
-    } else {
-        tree_potential_group<false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
-                                                              s->tree_uidx, s->tree_ufirst, e, e + g, lo);
-        tree_potential_alone<false><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st, s->tree_head,
-                                                              s->tree_uidx, s->tree_ufirst, e + 2 * (size_t)g, e + 3 * (size_t)g, lo);
-    }
+    const float2 *aprev = (const float2 *)s->acc;           // REL: the predicate of a force evaluation issued now: acc[] of this moment, read only
+    with_flags([&](auto quad, auto rel) {
+        tree_potential_group<quad, rel><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st,
+                                                                  s->tree_head, s->tree_uidx, s->tree_ufirst, e, e + g, lo, qm, aprev, s->tree_alpha);
+        tree_potential_alone<quad, rel><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st,
+                                                                  s->tree_head, s->tree_uidx, s->tree_ufirst, e + 2 * (size_t)g,
+                                                                  e + 3 * (size_t)g, lo, qm, aprev, s->tree_alpha);
+    }, s->tree_quad, tree_rel_active(s));
     HIPCHK(hipGetLastError());
     return NB_OK;
 }

@@ -307,24 +307,17 @@ void tree_emit(const uint64_t *__restrict__ uhi, const uint64_t *__restrict__ ul
 }
 
 // Centres of mass of the branches of depth `level` (launched for level = TREE_DEPTH_CAP - 1 ... 0): Quadtree.hpp:236-258.
-// QUAD (NB_FLAG_TREE_QUADRUPOLE; the one trailing argument is then the moment array, one {xx, xy, yy, 0} per node, +16 B per node =
-// +256 B per body on top of the 535 B of a tree handle, allocated for such a handle only): the raw second moment
+// QUAD (NB_FLAG_TREE_QUADRUPOLE; qm is the moment array, one {xx, xy, yy, 0} per node, +16 B per node = +256 B per body on top of
+// the 535 B of a tree handle, allocated for such a handle only; without QUAD it is a null pointer nobody reads): the raw second moment
 // M = sum m_k (y_k - c)(y_k - c)^T of the branch about the centre of mass c just stored, from its children's moments (the earlier
 // launch) moved to c by the parallel-axis term, children 0..3 in order, no contraction (tests/tree_quad_model.py restates it bit
 // for bit).  A leaf or an empty quadrant has M = 0: the pass writes its record when it visits the parent.
-__device__ __forceinline__ float4 *tree_moments() { return nullptr; }
-__device__ __forceinline__ float4 *tree_moments(float4 *qm) { return qm; }
-__device__ __forceinline__ const float4 *tree_moments(const float4 *qm) { return qm; }
-template <typename... T>                                    // (the REL forms below: the moment array comes first, their own arguments after it)
-__device__ __forceinline__ const float4 *tree_moments(const float4 *qm, T...) { return qm; }
-
-template <bool QUAD, typename... M>
+template <bool QUAD>
 __global__ __launch_bounds__(256)
 void tree_com(float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint8_t *__restrict__ dp, uint32_t level,
-              const TreeStats *__restrict__ st, M... moments)
+              const TreeStats *__restrict__ st, float4 *__restrict__ qm)
 {
 #pragma clang fp contract(off)
-    static_assert(sizeof...(M) == (QUAD ? 1 : 0), "the moment array is the argument of the QUAD form alone");
     if (st->fail || level >= st->max_depth) return;
     const uint32_t total = (uint32_t)st->nodes;
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
@@ -344,7 +337,6 @@ void tree_com(float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const ui
         }
         nd[i] = make_float4(sx, sy, sm, nd[i].w);
         if constexpr (QUAD) {
-            float4 *__restrict__ qm = tree_moments(moments...);
             float xx = 0.f, xy = 0.f, yy = 0.f;
             c = i + 1u;
             for (int q = 0; q < 4 && c < total; ++q) {
@@ -370,14 +362,16 @@ void tree_com(float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const ui
 // LEAVES (NB_FLAG_TREE_LEAVES): a leaf that is not accepted adds its own term (its record is exact: one position, the summed
 // mass), so every inserted body is counted once, in an accepted cell or as its leaf, and theta -> 0 is the direct sum.  The
 // nodes visited are the same; an empty quadrant (mass 0) adds nothing and costs no rsqrt.
-// QUAD (NB_FLAG_TREE_QUADRUPOLE, with LEAVES; the one trailing argument is then tree_com<true>'s moment array): an accepted BRANCH
+// Every walk kernel ends in (qm, alpha) and every potential kernel in (lo, qm, aprev, alpha), whatever its flags: qm, tree_com<true>'s
+// moment array, is read under QUAD only, and alpha (with aprev = acc[] in the potential kernels) under REL only.  A handle without
+// the flag passes a null qm and whatever alpha it holds; neither is touched.
+// QUAD (NB_FLAG_TREE_QUADRUPOLE, with LEAVES): an accepted BRANCH
 // adds, with d = com - body, R^2 = d^2 + eps^2, M its raw second moment,
 //     d * (m R^-3 + 7.5 (d^T M d) R^-7 - 1.5 tr(M) R^-5) - 3 (M d) R^-5
 // (the second-order term of the softened potential about the centre of mass; the dipole vanishes there).  The record is loaded on
 // acceptance of a branch only; the nodes visited and the acceptance test are unchanged, and a leaf's term, accepted or not, is
 // the monopole term above, instruction for instruction.
-// REL (NB_FLAG_TREE_RELATIVE, with LEAVES; after the moment array, if any, the trailing arguments are then alpha — the walks — or
-// the acc[] array and alpha — the potential kernels): a node is accepted for a body when it passes the test above AND the
+// REL (NB_FLAG_TREE_RELATIVE, with LEAVES): a node is accepted for a body when it passes the test above AND the
 // acceleration-relative one, m size^2 < (g d^2) d^2 with g = alpha |a_prev| of that body, i.e. G m size^2 / d^4 < alpha |a_prev|
 // with G = 1 (the opening criterion of GADGET-2).  a_prev is acc[] as the handle holds it: the walks read acc[b] once, before the
 // loop, in the thread that overwrites it at the end (no second array, no ordering problem); g is float32, one rounding per
@@ -399,12 +393,24 @@ __device__ __forceinline__ float tree_rel_g(float2 a, float alpha)
     return alpha * __builtin_sqrtf(a.x * a.x + a.y * a.y);
 }
 
-__device__ __forceinline__ float tree_rel_alpha(float alpha) { return alpha; }
-__device__ __forceinline__ float tree_rel_alpha(const float4 *, float alpha) { return alpha; }
-__device__ __forceinline__ float tree_rel_alpha(const float2 *, float alpha) { return alpha; }
-__device__ __forceinline__ float tree_rel_alpha(const float4 *, const float2 *, float alpha) { return alpha; }
-__device__ __forceinline__ const float2 *tree_rel_aprev(const float2 *aprev, float) { return aprev; }
-__device__ __forceinline__ const float2 *tree_rel_aprev(const float4 *, const float2 *aprev, float) { return aprev; }
+// the monopole term of a node of mass m at displacement (dx, dy): the two bodies of tree_walk_one's `term`, for the group walk
+template <int RSQ>
+__device__ __forceinline__ void tree_mono_term(float m, float dx, float dy, float d2, float eps2, float &sx, float &sy)
+{
+    if constexpr (RSQ == RSQ_QUAKE) {
+#pragma clang fp contract(off)
+        const float inv = quake_rsqrt(d2 + eps2);
+        const float inv3 = inv * inv * inv;
+        const float s = m * inv3;
+        sx = sx + dx * s;
+        sy = sy + dy * s;
+    } else {
+        const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
+        const float s = m * (inv * inv * inv);
+        sx = __builtin_fmaf(dx, s, sx);
+        sy = __builtin_fmaf(dy, s, sy);
+    }
+}
 
 template <int RSQ>
 __device__ __forceinline__ void tree_quad_term(float4 q, float4 m, float dx, float dy, float d2, float eps2, float &sx, float &sy)
@@ -429,18 +435,18 @@ __device__ __forceinline__ void tree_quad_term(float4 q, float4 m, float dx, flo
     }
 }
 
-template <int RSQ, bool LEAVES, bool QUAD, bool REL, typename... M>
+template <int RSQ, bool LEAVES, bool QUAD, bool REL>
 __device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restrict__ nd, const uint32_t *__restrict__ nx,
                                               const uint32_t *__restrict__ val, const float2 *__restrict__ pos, float eps2, float theta2,
-                                              float2 *__restrict__ acc, const TreeStats *__restrict__ st, M... moments)
+                                              float2 *__restrict__ acc, const TreeStats *__restrict__ st,
+                                              const float4 *__restrict__ qm, float alpha)
 {
-    static_assert(sizeof...(M) == (QUAD ? 1 : 0) + (REL ? 1 : 0) && (LEAVES || !(QUAD || REL)),
-                  "the moment array is the argument of the QUAD form alone, alpha that of the REL form");
+    static_assert(LEAVES || !(QUAD || REL), "the moments and the relative test belong to the convergent walk");
     const uint32_t b = val[i];
     const float2 p = pos[b];
     const uint32_t total = (uint32_t)st->nodes;
     float g = 0.f;
-    if constexpr (REL) g = tree_rel_g(acc[b], tree_rel_alpha(moments...));
+    if constexpr (REL) g = tree_rel_g(acc[b], alpha);
     float sx = 0.f, sy = 0.f;
     uint32_t node = 0;
     while (node < total) {
@@ -474,7 +480,7 @@ __device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restri
                 const uint32_t next = nx[node];
                 if (d2 > 0.f) {
                     if (next == node + 1u) term();
-                    else tree_quad_term<RSQ>(q, tree_moments(moments...)[node], dx, dy, d2, eps2, sx, sy);
+                    else tree_quad_term<RSQ>(q, qm[node], dx, dy, d2, eps2, sx, sy);
                 }
                 node = next > node ? next : node + 1u;
             } else {
@@ -492,15 +498,15 @@ __device__ __forceinline__ void tree_walk_one(uint32_t i, const float4 *__restri
     acc[b] = make_float2(sx, sy);
 }
 
-template <int RSQ, bool LEAVES, bool QUAD, bool REL = false, typename... M>
+template <int RSQ, bool LEAVES, bool QUAD, bool REL>
 __global__ __launch_bounds__(256)
 void tree_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
-               const TreeStats *__restrict__ st, M... moments)
+               const TreeStats *__restrict__ st, const float4 *__restrict__ qm, float alpha)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || st->fail) return;
-    tree_walk_one<RSQ, LEAVES, QUAD, REL>(i, nd, nx, val, pos, eps2, theta2, acc, st, moments...);
+    tree_walk_one<RSQ, LEAVES, QUAD, REL>(i, nd, nx, val, pos, eps2, theta2, acc, st, qm, alpha);
 }
 
 // The wave-uniform walk of NB_FLAG_TREE_LEAVES with NB_RSQRT_EXACT: one wave is one group, the 64 bodies at sorted positions
@@ -523,33 +529,32 @@ __device__ __forceinline__ bool tree_lane_alone(uint32_t i, const uint32_t *__re
     return (ufirst[(uint32_t)uidx[i] - 1u] >> 6) != (i >> 6);        // (not a head: at least one key starts before i)
 }
 
-template <bool QUAD, bool REL = false, typename... M>
+template <bool QUAD, bool REL>
 __global__ __launch_bounds__(256)
 void tree_walk_alone(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                      const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
                      const TreeStats *__restrict__ st, const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
-                     const uint32_t *__restrict__ ufirst, M... moments)
+                     const uint32_t *__restrict__ ufirst, const float4 *__restrict__ qm, float alpha)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || st->fail || !tree_lane_alone(i, head, uidx, ufirst, st)) return;
-    tree_walk_one<RSQ_EXACT, true, QUAD, REL>(i, nd, nx, val, pos, eps2, theta2, acc, st, moments...);
+    tree_walk_one<RSQ_EXACT, true, QUAD, REL>(i, nd, nx, val, pos, eps2, theta2, acc, st, qm, alpha);
 }
 
-template <bool QUAD, bool REL = false, typename... M>
+template <bool QUAD, bool REL>
 __global__ __launch_bounds__(256)
 void tree_walk_group(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                      const float2 *__restrict__ pos, uint32_t n, float eps2, float theta2, float2 *__restrict__ acc,
                      const TreeStats *__restrict__ st, const uint32_t *__restrict__ head, const uint64_t *__restrict__ uidx,
-                     const uint32_t *__restrict__ ufirst, M... moments)
+                     const uint32_t *__restrict__ ufirst, const float4 *__restrict__ qm, float alpha)
 {
-    static_assert(sizeof...(M) == (QUAD ? 1 : 0) + (REL ? 1 : 0), "the moment array is the argument of the QUAD form alone, alpha that of the REL form");
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || st->fail || tree_lane_alone(i, head, uidx, ufirst, st)) return;
     const uint32_t b = val[i];
     const float2 p = pos[b];
     const uint32_t total = (uint32_t)st->nodes;
     float g = 0.f;
-    if constexpr (REL) g = tree_rel_g(acc[b], tree_rel_alpha(moments...));
+    if constexpr (REL) g = tree_rel_g(acc[b], alpha);
     float sx = 0.f, sy = 0.f;
     uint32_t node = 0;
     while (node < total) {
@@ -569,23 +574,13 @@ void tree_walk_group(const float4 *__restrict__ nd, const uint32_t *__restrict__
         const bool leaf = next == node + 1u;
         if constexpr (QUAD) {
             if (all_far && !leaf) {
-                const float4 m = tree_moments(moments...)[node];
+                const float4 m = qm[node];
                 if (d2 > 0.f) tree_quad_term<RSQ_EXACT>(q, m, dx, dy, d2, eps2, sx, sy);
             } else if (leaf && (all_far || q.z != 0.f)) {
-                if (d2 > 0.f) {
-                    const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
-                    const float s = q.z * (inv * inv * inv);
-                    sx = __builtin_fmaf(dx, s, sx);
-                    sy = __builtin_fmaf(dy, s, sy);
-                }
+                if (d2 > 0.f) tree_mono_term<RSQ_EXACT>(q.z, dx, dy, d2, eps2, sx, sy);
             }
         } else if (all_far || (leaf && q.z != 0.f)) {
-            if (d2 > 0.f) {
-                const float inv = __builtin_amdgcn_rsqf(d2 + eps2);
-                const float s = q.z * (inv * inv * inv);
-                sx = __builtin_fmaf(dx, s, sx);
-                sy = __builtin_fmaf(dy, s, sy);
-            }
+            if (d2 > 0.f) tree_mono_term<RSQ_EXACT>(q.z, dx, dy, d2, eps2, sx, sy);
         }
         node = all_far && next > node ? next : node + 1u;    // (a leaf's next is node + 1)
     }
@@ -695,15 +690,15 @@ __device__ __forceinline__ void tree_energy_of(uint32_t b, double phi, const flo
 }
 
 // the lanes tree_lane_alone takes out of their windows, massless ones excepted: the per-lane walk of tree_walk_one<.., true, QUAD>
-template <bool QUAD, bool REL = false, typename... M>
+template <bool QUAD, bool REL>
 __global__ __launch_bounds__(256)
 void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                           const float2 *__restrict__ pos, const float2 *__restrict__ vel, const float *__restrict__ mass, uint32_t n,
                           double eps2, float theta2, const TreeStats *__restrict__ st, const uint32_t *__restrict__ head,
                           const uint64_t *__restrict__ uidx, const uint32_t *__restrict__ ufirst, double *__restrict__ ksum,
-                          double *__restrict__ usum, const float *__restrict__ lo, M... moments)
+                          double *__restrict__ usum, const float *__restrict__ lo, const float4 *__restrict__ qm,
+                          const float2 *__restrict__ aprev, float alpha)
 {
-    static_assert(sizeof...(M) == (QUAD ? 1 : 0) + (REL ? 2 : 0), "the moment array is the argument of the QUAD form alone, acc[] and alpha those of the REL form");
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     double k = 0.0, u = 0.0;
     if (i < n && !st->fail && i < st->massive && tree_lane_alone(i, head, uidx, ufirst, st)) {
@@ -711,7 +706,7 @@ void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restr
         const float2 p = pos[b];
         const uint32_t total = (uint32_t)st->nodes;
         float g = 0.f;
-        if constexpr (REL) g = tree_rel_g(tree_rel_aprev(moments...)[b], tree_rel_alpha(moments...));
+        if constexpr (REL) g = tree_rel_g(aprev[b], alpha);
         double phi = 0.0;
         uint32_t node = 0;
         while (node < total) {
@@ -730,7 +725,7 @@ void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restr
             if (far) {
                 if (d2 > 0.f) {
                     if constexpr (QUAD) phi += leaf ? tree_potential_mono(q, tree_potential_mass(q, leaf, node, lo), p, eps2)
-                                                    : tree_potential_quad(q, tree_moments(moments...)[node], p, eps2);
+                                                    : tree_potential_quad(q, qm[node], p, eps2);
                     else phi += tree_potential_mono(q, tree_potential_mass(q, leaf, node, lo), p, eps2);
                 }
                 node = next > node ? next : node + 1u;
@@ -748,15 +743,15 @@ void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restr
 // the windows: tree_walk_group's loop (node index through readfirstlane, one ballot, the moment record loaded inside the
 // wave-uniform accepted-branch path).  The lanes that take no part stay out of the loop, so they neither vote nor lead, and
 // join the block reduction with zeros.
-template <bool QUAD, bool REL = false, typename... M>
+template <bool QUAD, bool REL>
 __global__ __launch_bounds__(256)
 void tree_potential_group(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                           const float2 *__restrict__ pos, const float2 *__restrict__ vel, const float *__restrict__ mass, uint32_t n,
                           double eps2, float theta2, const TreeStats *__restrict__ st, const uint32_t *__restrict__ head,
                           const uint64_t *__restrict__ uidx, const uint32_t *__restrict__ ufirst, double *__restrict__ ksum,
-                          double *__restrict__ usum, const float *__restrict__ lo, M... moments)
+                          double *__restrict__ usum, const float *__restrict__ lo, const float4 *__restrict__ qm,
+                          const float2 *__restrict__ aprev, float alpha)
 {
-    static_assert(sizeof...(M) == (QUAD ? 1 : 0) + (REL ? 2 : 0), "the moment array is the argument of the QUAD form alone, acc[] and alpha those of the REL form");
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     double k = 0.0, u = 0.0;
     if (i < n && !st->fail && !tree_lane_alone(i, head, uidx, ufirst, st)) {
@@ -764,7 +759,7 @@ void tree_potential_group(const float4 *__restrict__ nd, const uint32_t *__restr
         const float2 p = pos[b];
         const uint32_t total = (uint32_t)st->nodes;
         float g = 0.f;
-        if constexpr (REL) g = tree_rel_g(tree_rel_aprev(moments...)[b], tree_rel_alpha(moments...));
+        if constexpr (REL) g = tree_rel_g(aprev[b], alpha);
         double phi = 0.0;
         uint32_t node = 0;
         while (node < total) {
@@ -784,7 +779,7 @@ void tree_potential_group(const float4 *__restrict__ nd, const uint32_t *__restr
             const bool leaf = next == node + 1u;
             if constexpr (QUAD) {
                 if (all_far && !leaf) {
-                    const float4 m = tree_moments(moments...)[node];
+                    const float4 m = qm[node];
                     if (d2 > 0.f) phi += tree_potential_quad(q, m, p, eps2);
                 } else if (leaf && (all_far || q.z != 0.f)) {
                     const double m = tree_potential_mass(q, leaf, node, lo);       // (wave-uniform: one scalar load)

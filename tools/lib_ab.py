@@ -7,7 +7,9 @@ final bodies compared bit for bit (sha256 of pos | vel | acc) and timed.  For ch
 
 A case is [MODS-]BASE<n>.  BASE: p 2-D fp32, d 2-D fp64, q 3-D fp32, qd 3-D fp64, ref the reference start.  MODS, letters
 in any order: o one-sided (symmetry=False), g eps = 0 (the guarded body, one-sided), k rsqrt="quake", s mass scaling in the
-individual-masses run (uniform_mass=False, mass_scaling=True).  Example: og-qd4096, os-p65536.
+individual-masses run (uniform_mass=False, mass_scaling=True); the Barnes-Hut force: t force="tree" at theta = 0.5, l tree_leaves=True,
+u tree_quadrupole=True, r tree_alpha=0.02, e tree_energy=True (the hash then also covers the two doubles of energy() read after the
+steps).  Example: og-qd4096, os-p65536, tlur-p4096.  A combination Simulation rejects ends the run with its message.
 
 (the Python binding loads $NBODY_HIP_LIB when set — the LIBRARY reads no environment variables; each side runs in a child process)
 """
@@ -15,6 +17,7 @@ import argparse
 import hashlib
 import json
 import os
+import struct
 import subprocess
 import sys
 import time
@@ -47,13 +50,27 @@ def child(cases, steps):
             kw["eps"] = 0.0
         if "k" in mods:
             kw["rsqrt"] = "quake"
+        if "t" in mods:
+            kw.update(force="tree", theta=0.5)
+        if "l" in mods:
+            kw["tree_leaves"] = True
+        if "u" in mods:
+            kw["tree_quadrupole"] = True
+        if "r" in mods:
+            kw["tree_alpha"] = 0.02
+        if "e" in mods:
+            kw["tree_energy"] = True
         for general in (False, True):
             k = dict(kw)
             if general:
                 k["uniform_mass"] = False
                 if "s" in mods:
                     k["mass_scaling"] = True
-            with nb.Simulation(ic, **k) as s:
+            try:
+                sim = nb.Simulation(ic, **k)
+            except ValueError as err:                # a combination of letters it rejects
+                sys.exit(f"{name}: {err}")
+            with sim as s:
                 s.advance(30, dt)
                 s.wait()
                 t0 = time.perf_counter()
@@ -61,7 +78,10 @@ def child(cases, steps):
                 s.wait()
                 el = (time.perf_counter() - t0) / steps
                 b = s.sync()
-                h = hashlib.sha256(b"".join(np.ascontiguousarray(b[f]).tobytes() for f in ("pos", "vel", "acc"))).hexdigest()
+                data = b"".join(np.ascontiguousarray(b[f]).tobytes() for f in ("pos", "vel", "acc"))
+                if "e" in mods:
+                    data += struct.pack("dd", *s.energy())
+                h = hashlib.sha256(data).hexdigest()
             out[f"{name}/{'individual' if general else 'equal'} masses"] = (h, el * 1e6)
     print(json.dumps(out))
 
