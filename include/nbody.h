@@ -75,6 +75,42 @@ _Static_assert(offsetof(nb_body, vel) == 16 && offsetof(nb_body, acc) == 32 &&
                "Body field offsets");
 #endif
 
+/* ---- tree node record -----------------------------------------------------
+ * Bit-compatible with the reference's `struct alignas(32) Node` (headers/Node.hpp:31-53): the anonymous alignas(16)
+ * `data` {Vec2 pos; float mass; Quad quad}, Quad = {Vec2 center; float size} (headers/Quad.hpp), then five size_t.
+ * sizeof 128, alignof 32 (measured with g++ and clang, -std=c++20 — tests/golden/node_layout.json).  nb_tree_nodes
+ * (below) fills these; the library writes every padding byte as zero. */
+typedef struct nb_tree_node {
+    nb_vec2  pos;           /* offset   0  Node::data.pos: centre of mass (branch) / position (leaf) / (0, 0) (empty quadrant) */
+    float    mass;          /* offset  16  Node::data.mass */
+    float    _pad0[3];
+    nb_vec2  center;        /* offset  32  Node::data.quad.center */
+    float    size;          /* offset  48  Node::data.quad.size */
+    float    _pad1[3];
+    uint64_t children;      /* offset  64  Node::children: index of the first of four consecutive children; 0 = leaf / empty quadrant */
+    uint64_t next;          /* offset  72  Node::next: the node a walk goes to when it skips this subtree; 0 = none (the end) */
+    uint64_t bodies_start;  /* offset  80  Node::bodies.start: 0 (the reference's leaf ranges are empty) */
+    uint64_t bodies_end;    /* offset  88  Node::bodies.end:   0 */
+    uint64_t depth;         /* offset  96  Node::depth: 0 for the root */
+    uint64_t _pad2[3];      /* tail padding of alignas(32) */
+} nb_tree_node;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_tree_node) == 128, "Node is 128 bytes (Node.hpp:31)");
+static_assert(offsetof(nb_tree_node, mass) == 16 && offsetof(nb_tree_node, center) == 32 && offsetof(nb_tree_node, size) == 48 &&
+              offsetof(nb_tree_node, children) == 64 && offsetof(nb_tree_node, next) == 72 &&
+              offsetof(nb_tree_node, bodies_start) == 80 && offsetof(nb_tree_node, bodies_end) == 88 &&
+              offsetof(nb_tree_node, depth) == 96,
+              "Node field offsets");
+#else
+_Static_assert(sizeof(nb_tree_node) == 128, "Node is 128 bytes (Node.hpp:31)");
+_Static_assert(offsetof(nb_tree_node, mass) == 16 && offsetof(nb_tree_node, center) == 32 && offsetof(nb_tree_node, size) == 48 &&
+               offsetof(nb_tree_node, children) == 64 && offsetof(nb_tree_node, next) == 72 &&
+               offsetof(nb_tree_node, bodies_start) == 80 && offsetof(nb_tree_node, bodies_end) == 88 &&
+               offsetof(nb_tree_node, depth) == 96,
+               "Node field offsets");
+#endif
+
 /* ---- enums ---------------------------------------------------------------- */
 enum { NB_OK = 0, NB_EINVAL = -1, NB_ENODEVICE = -2, NB_EHIP = -3, NB_ENOMEM = -4,
        NB_EIO = -5, NB_EFORMAT = -6, NB_ESTATE = -7 };
@@ -133,7 +169,7 @@ enum { NB_FORCE_DIRECT = 0,    /* every pair: the kernels this library is built 
                                   followed for 63 levels; an evaluation that needs more integrates nothing (positions and velocities
                                   stay; with NB_EXTRA_COLLIDE the collision pass of that step still runs, on the unchanged
                                   positions), and the next synchronising call (nb_wait, nb_sync, nb_sync_positions, nb_energy,
-                                  nb_momentum, nb_tree_stats) returns NB_ENOMEM once, naming the frame and what was needed.
+                                  nb_momentum, nb_tree_stats, nb_tree_nodes) returns NB_ENOMEM once, naming the frame and what was needed.
                                   nb_momentum stays the exact O(n) diagnostic.  nb_energy is the exact O(n^2) fp64 pair sweep of a
                                   direct-sum handle (at the sizes the tree exists for one reading costs as much as many steps)
                                   unless the handle has NB_FLAG_TREE_ENERGY (flags, below): it then walks the tree, O(n log n) */
@@ -437,6 +473,35 @@ int nb_collision_stats(nb_sim *s, uint64_t *pairs_last_step, uint64_t *pairs_tot
  * evaluation and the evaluations that failed (node capacity, depth cap) since creation; any pointer may be NULL; NB_ESTATE
  * on a NB_FORCE_DIRECT handle. */
 int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, uint64_t *overflow_steps);
+
+/* The reference's `quadtree.nodes` (Quadtree.hpp:14; copied by its caller every frame, main.cpp:626, and drawn by
+ * drawQuadtreeNode, main.cpp:394-475): the tree of the MOST RECENT BUILD on the handle as Node records.  The most recent build is
+ * the force evaluation of the last nb_step / nb_accelerations, or an nb_energy on a NB_FLAG_TREE_ENERGY handle; after nb_step that
+ * is the tree of the positions BEFORE the drift, as the reference's quadtree.nodes after step().  Any tree handle, any of the four
+ * tree flags, either rsqrt mode: the tree does not depend on them (quadrupole moments are not exported: Node has no field).
+ * REFERENCE FORM (the reference's own indices follow the insertion order and cannot be reproduced; this is the one numbering with
+ * its invariants that does not depend on the order of the bodies): node 0 is the root; the branches are ranked r = 0, 1, ... in
+ * pre-order and the children of branch r are nodes 1 + 4 r ... 1 + 4 r + 3 in quadrant order, so *count = 1 + 4 x branches = the
+ * `nodes` of nb_tree_stats; children = index of the first child, 0 for a leaf or an empty quadrant; next = own index + 1 for
+ * quadrants 0..2 and the parent's next for quadrant 3, 0 for the root (Quadtree.hpp:71-75); depth as the reference counts it;
+ * bodies = {0, 0}; pos / mass the node's record as the build holds it (a branch: centre of mass and mass; a leaf: its position and
+ * summed mass; an empty quadrant: 0, 0, 0); size = the root size halved depth times (size * size has the bits the walk tests);
+ * center = the root centre carried down with Quad::into_quadrant's arithmetic (Quad.hpp:51-57).  The tree is the reference's own
+ * (same cells, same records, following `children`), and Quadtree::acc over this array gives the bits of the handle's walk
+ * (tests/tree_nodes_model.py).
+ * The call synchronises.  count may not be NULL and is written whenever the call returns NB_OK or NB_EINVAL for the capacity:
+ * out == NULL is the count query (NB_OK); out != NULL with capacity < *count is NB_EINVAL naming both numbers, nothing written to
+ * out; before any build *count = 0, NB_OK.  NB_ESTATE on a NB_FORCE_DIRECT handle.  A pending failed-build report (node capacity,
+ * depth cap) is delivered by this call like by nb_wait: NB_ENOMEM, once; while the last build is a failed one, later calls return
+ * NB_ESTATE ("no tree to export").  out may be any host memory, as for nb_sync: ranges known to be page-locked (nb_host_alloc /
+ * nb_host_register) are written by the copy engine directly, anything else moves through a page-locked staging buffer of the
+ * library's.  Nothing of the handle changes: tree arrays, acc[], positions, velocities, frame counter and nb_tree_stats are
+ * untouched, and the next force evaluation is bit-identical to one on a handle that never called this.
+ * Memory: nothing until the first call with out != NULL; then, sized by the node count of the build exported (growth only, freed by
+ * nb_destroy; NOT by the node capacity 16 n + 4096): 144 bytes per node on the device (the record 128, branch flag 4, branch rank 8,
+ * export index 4) plus the scan's temporary storage, and 128 bytes per node of page-locked host staging once a destination needs
+ * it.  With nb_profile_enable the export kernels are bracketed like a force launch and count as one (nb_profile_read). */
+int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size_t *count);
 
 /* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
  * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without

@@ -60,6 +60,23 @@ BODY3_DTYPE = np.dtype(
 )
 
 
+#: numpy view of the reference's 128-byte ``Node`` record (Node.hpp:31-53; ``nb_tree_node`` of include/nbody.h), as
+#: ``nb_tree_nodes`` fills it: every byte no field covers is zero
+NODE_DTYPE = np.dtype(
+    {
+        "names": ["pos", "mass", "center", "size", "children", "next", "bodies_start", "bodies_end", "depth"],
+        "formats": [(np.float32, 2), np.float32, (np.float32, 2), np.float32, np.uint64, np.uint64, np.uint64, np.uint64, np.uint64],
+        "offsets": [0, 16, 32, 48, 64, 72, 80, 88, 96],
+        "itemsize": 128,
+    }
+)
+
+
+def nodes_array(n: int) -> np.ndarray:
+    """Zero-initialised array of n 128-byte Node records (padding zero)."""
+    return np.zeros(n * NODE_DTYPE.itemsize, dtype=np.uint8).view(NODE_DTYPE)
+
+
 class NBodyError(RuntimeError):
     """Raised for every non-zero status / NULL handle coming out of the C ABI."""
 
@@ -173,6 +190,7 @@ PROTOTYPES = {
     "nb_collide_capacity": (C.c_int, [C.c_void_p, C.c_size_t]),
     "nb_collision_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "nb_tree_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "nb_tree_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nb_tree_alpha": (C.c_int, [C.c_void_p, C.c_float]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),

@@ -198,6 +198,16 @@ struct nb_sim {
     size_t tree_tmp_bytes = 0;
     TreeStats *tree_stats = nullptr;           // device
     TreeStats *tree_host = nullptr;            // page-locked mirror
+    // nb_tree_nodes (the export kernels of nb_tree.hip.h): nothing below exists before the first call; grown by the node count exported
+    uint64_t tree_exp_cap = 0;                 // nodes the four arrays below hold
+    uint4 *tree_exp_rec = nullptr;             // the records, 128 B per node
+    uint32_t *tree_exp_flag = nullptr;         // 1 where a pre-order node is a branch ...
+    uint64_t *tree_exp_rank = nullptr;         // ... and the prefix sum: its rank among the branches
+    uint32_t *tree_exp_idx = nullptr;          // export index of a pre-order node
+    void *tree_exp_tmp = nullptr;              // rocprim temporary storage of that scan (asked for this element count)
+    size_t tree_exp_tmp_bytes = 0;
+    void *tree_exp_stage = nullptr;            // page-locked host staging for destinations the library does not know to be page-locked
+    uint64_t tree_exp_stage_cap = 0;           // nodes it holds
 
     // profiling
     bool prof = false;
@@ -699,6 +709,9 @@ static void free_all(nb_sim *s)
                     (void *)s->tree_stats})
         (void)hipFree(q);
     if (s->tree_host) (void)hipHostFree(s->tree_host);
+    for (void *q : {(void *)s->tree_exp_rec, (void *)s->tree_exp_flag, (void *)s->tree_exp_rank, (void *)s->tree_exp_idx, s->tree_exp_tmp})
+        (void)hipFree(q);
+    if (s->tree_exp_stage) (void)hipHostFree(s->tree_exp_stage);
     if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
     if (s->ev_packed) (void)hipEventDestroy(s->ev_packed);
     if (s->ev_copied) (void)hipEventDestroy(s->ev_copied);
@@ -2092,6 +2105,72 @@ extern "C" int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, ui
     if (max_depth) *max_depth = s->tree_host->max_depth;
     if (overflow_steps) *overflow_steps = s->tree_host->overflow_steps;
     return rc;
+}
+
+// Scratch of nb_tree_nodes for `total` nodes: 144 B per node on the device (record 128, flag 4, rank 8, index 4) plus the scan's
+// temporary storage, asked from nb_tree_scan for THIS element count (tree_tmp was sized for n + 2 elements).  Growth only, with an
+// eighth of slack so that a tree that grows a little every frame does not reallocate every frame; never above the node capacity.
+static int tree_export_alloc(nb_sim *s, uint64_t total)
+{
+    if (total <= s->tree_exp_cap) return NB_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    for (void *q : {(void *)s->tree_exp_rec, (void *)s->tree_exp_flag, (void *)s->tree_exp_rank, (void *)s->tree_exp_idx, s->tree_exp_tmp})
+        (void)hipFree(q);
+    s->tree_exp_rec = nullptr; s->tree_exp_flag = nullptr; s->tree_exp_rank = nullptr; s->tree_exp_idx = nullptr; s->tree_exp_tmp = nullptr;
+    s->tree_exp_cap = 0;
+    const uint64_t cap = std::max<uint64_t>(total, std::min<uint64_t>(total + total / 8 + 1024, s->tree_cap));
+    HIPCHK(hipMalloc((void **)&s->tree_exp_rec, cap * sizeof(nb_tree_node)));
+    HIPCHK(hipMalloc((void **)&s->tree_exp_flag, cap * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_exp_rank, cap * sizeof(uint64_t)));
+    HIPCHK(hipMalloc((void **)&s->tree_exp_idx, cap * sizeof(uint32_t)));
+    size_t bytes = 0;
+    HIPCHK(nb_tree_scan(nullptr, bytes, s->tree_exp_flag, s->tree_exp_rank, (size_t)cap, s->stream));
+    s->tree_exp_tmp_bytes = std::max<size_t>(bytes, 256);
+    HIPCHK(hipMalloc(&s->tree_exp_tmp, s->tree_exp_tmp_bytes));
+    s->tree_exp_cap = cap;
+    return NB_OK;
+}
+
+// The reference's `quadtree.nodes` (main.cpp:626, drawQuadtreeNode main.cpp:394-475) for the tree of the last build.
+extern "C" int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size_t *count)
+{
+    if (!s || !count) return nb_fail(NB_EINVAL, "nb_tree_nodes: NULL %s", !s ? "handle" : "count");
+    if (!s->tree) return nb_fail(NB_ESTATE, "nb_tree_nodes: the handle was created with NB_FORCE_DIRECT");
+    if (s->in_step) return nb_fail(NB_ESTATE, "nb_tree_nodes: a split step is in flight");
+    if (bind(s)) return NB_EHIP;
+    { const int rc = step_check(s); if (rc) return rc; }          // synchronises; a pending failed-build report leaves through here, once
+    const TreeStats &t = *s->tree_host;
+    if (t.fail)
+        return nb_fail(NB_ESTATE, "nb_tree_nodes: no tree to export: the last build failed (%s)", t.fail == 1 ? "node capacity" : "depth cap");
+    const uint64_t total = t.nodes;                               // 0 before any build; <= tree_cap < 2^32 after a good one
+    if (total > s->tree_cap) return nb_fail(NB_ESTATE, "internal: nb_tree_nodes: %llu nodes in a capacity of %llu", (unsigned long long)total, (unsigned long long)s->tree_cap);
+    *count = (size_t)total;
+    if (!out || total == 0) return NB_OK;
+    if (capacity < total)
+        return nb_fail(NB_EINVAL, "nb_tree_nodes: the tree has %llu nodes, out holds %zu", (unsigned long long)total, capacity);
+    { const int rc = tree_export_alloc(s, total); if (rc) return rc; }
+    const size_t bytes = (size_t)total * sizeof(nb_tree_node);
+    const bool direct = pinned_covers(out, bytes);
+    if (!direct && s->tree_exp_stage_cap < total) {
+        if (s->tree_exp_stage) { (void)hipHostFree(s->tree_exp_stage); s->tree_exp_stage = nullptr; s->tree_exp_stage_cap = 0; }
+        HIPCHK(hipHostMalloc(&s->tree_exp_stage, (size_t)s->tree_exp_cap * sizeof(nb_tree_node), hipHostMallocDefault));
+        s->tree_exp_stage_cap = s->tree_exp_cap;
+    }
+    const uint32_t tot = (uint32_t)total;
+    const uint32_t g = (uint32_t)std::min<uint64_t>((total + 255u) / 256u, 8u * (uint32_t)s->cus);
+    std::pair<hipEvent_t, hipEvent_t> pr;                         // with nb_profile_enable the export kernels count as one launch
+    if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
+    tree_export_flags<<<g, 256, 0, s->stream>>>(s->tree_dp, tot, s->tree_exp_flag);
+    HIPCHK(hipGetLastError());
+    size_t tmp = s->tree_exp_tmp_bytes;
+    HIPCHK(nb_tree_scan(s->tree_exp_tmp, tmp, s->tree_exp_flag, s->tree_exp_rank, (size_t)total, s->stream));
+    tree_export_root<<<1, 64, 0, s->stream>>>(s->tree_nd, s->tree_dp, s->tree_root_dev, tot, s->tree_exp_rec, s->tree_exp_idx);
+    for (uint32_t level = 0; level < t.max_depth && level < (uint32_t)TREE_DEPTH_CAP; ++level)
+        tree_export_level<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, s->tree_exp_rank, level, tot, s->tree_exp_rec,
+                                                    s->tree_exp_idx);
+    HIPCHK(hipGetLastError());
+    if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
+    return copy_d2h(s, out, s->tree_exp_rec, bytes, s->stream, direct ? nullptr : s->tree_exp_stage);
 }
 
 // alpha travels to the walks as a kernel argument: the evaluations enqueued so far keep theirs, the next one takes the new value

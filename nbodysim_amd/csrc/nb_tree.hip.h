@@ -812,4 +812,85 @@ void tree_integrate(const float2 *__restrict__ pos_cur, float2 *__restrict__ pos
     kick_drift_one<L, STRICT>(acc[li], li, pos_cur, pos_next, vel, acc, 0u, dt_kick, dt_drift, extras, flags);
 }
 
+// ---- export ---------------------------------------------------------------------------------------------------------
+// nb_tree_nodes: the tree of the last build as the reference's `Node` records (Node.hpp:31-53, 128 bytes; nb_tree_node of
+// include/nbody.h), in REFERENCE FORM: node 0 is the root, the branches are ranked r = 0, 1, ... in pre-order and the four children
+// of branch r are nodes 1 + 4 r ... 1 + 4 r + 3 in quadrant order, the way Quadtree::insert allocates them (Quadtree.hpp:64-75).
+// These kernels read nd / nx / dp, TreeRoot and TreeStats only (never the keys) and write arrays of their own: the build's arrays,
+// and so the next force evaluation, do not know they ran.
+//   tree_export_flags     flag[i] = 1 where pre-order node i is a branch; an exclusive scan gives rank[i]
+//   tree_export_root      record 0 and idx[0] = 0 (idx: export index of a pre-order node)
+//   tree_export_level     for level = 0 ... max_depth - 1 (the host knows max_depth after the synchronisation): every branch of depth
+//                         `level` reads its own exported record (centre, size, next: written by the launch before), walks its four
+//                         children through nx like tree_com, and writes their complete records and their idx.  Top-down, no atomics.
+// A branch's four children are one contiguous 512-byte block: 8 lanes x one 16-byte store per record, 32 lanes per branch, two
+// branches per wave and round, so the block leaves as whole 128-byte lines (one lane per record would issue eight strided stores).
+// A wave looks at 64 pre-order nodes at a time, one per lane, and its two halves take the branches the ballot found, two by two.
+// The child centre is Quad::into_quadrant's arithmetic (Quad.hpp:51-57), the recurrence of tree_keys; size * size of depth d has the
+// bits of TreeRoot::s2[d] (halving is exact).  Padding bytes are written as zero.
+__global__ __launch_bounds__(256)
+void tree_export_flags(const uint8_t *__restrict__ dp, uint32_t total, uint32_t *__restrict__ flag)
+{
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) flag[i] = dp[i] >> 7;
+}
+
+__global__ __launch_bounds__(64)
+void tree_export_root(const float4 *__restrict__ nd, const uint8_t *__restrict__ dp, const TreeRoot *__restrict__ root, uint32_t total,
+                      uint4 *__restrict__ out, uint32_t *__restrict__ idx)
+{
+    const uint32_t part = threadIdx.x;
+    if (part >= 8u || total == 0u) return;
+    const float4 rec = nd[0];
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (part == 0u) { v.x = __float_as_uint(rec.x); v.y = __float_as_uint(rec.y); idx[0] = 0u; }
+    else if (part == 1u) v.x = __float_as_uint(rec.z);
+    else if (part == 2u) { v.x = __float_as_uint(root->cx); v.y = __float_as_uint(root->cy); }
+    else if (part == 3u) v.x = __float_as_uint(root->size);
+    else if (part == 4u) v.x = dp[0] >> 7;              // children: the first child of branch 0 is node 1; next stays 0 (Quadtree.hpp:32)
+    out[part] = v;
+}
+
+__global__ __launch_bounds__(256)
+void tree_export_level(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint8_t *__restrict__ dp,
+                       const uint64_t *__restrict__ rank, uint32_t level, uint32_t total, uint4 *__restrict__ out, uint32_t *__restrict__ idx)
+{
+#pragma clang fp contract(off)
+    const uint32_t lane = threadIdx.x & 63u, half = lane >> 5, q = (lane >> 3) & 3u, part = lane & 7u;
+    for (uint32_t base = blockIdx.x * 256u + (threadIdx.x & ~63u); base < total; base += gridDim.x * 256u) {   // (wave-uniform)
+        const uint32_t i = base + lane;
+        uint64_t todo = __ballot(i < total && dp[i] == ((uint8_t)level | TREE_BRANCH));
+        while (todo) {
+            const uint64_t rest = todo & (todo - 1ull);                      // the lower half takes the lowest branch, the upper the next
+            const uint64_t mine = half ? rest : todo;
+            todo = rest & (rest - 1ull);
+            if (!mine) continue;
+            const uint32_t b = base + (uint32_t)__builtin_ctzll(mine);       // the branch, a pre-order index (b < total: the ballot)
+            const uint32_t pe = idx[b];                                      // its export index and record
+            if (pe >= total) continue;                                       // (never: written by the launch before; keeps reads inside)
+            const uint4 pc = out[8u * pe + 2u], ps = out[8u * pe + 3u], pl = out[8u * pe + 4u];
+            uint32_t c = b + 1u;                                             // child q, through nx like tree_com
+            for (uint32_t k = 0; k < q && c < total; ++k) c = nx[c];
+            const uint32_t e = 1u + 4u * (uint32_t)rank[b] + q;              // (1 + 4 branches = total <= capacity < 2^32)
+            if (c >= total || e >= total) continue;                          // (never: a branch has four children, tree_emit)
+            const float4 rec = nd[c];
+            const bool branch = (dp[c] & TREE_BRANCH) != 0;
+            const float size = __uint_as_float(ps.x) * 0.5f;                 // Quad.hpp:51-57
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (part == 0u) { v.x = __float_as_uint(rec.x); v.y = __float_as_uint(rec.y); idx[c] = e; }
+            else if (part == 1u) v.x = __float_as_uint(rec.z);
+            else if (part == 2u) {
+                v.x = __float_as_uint(__uint_as_float(pc.x) + ((float)(q & 1u) - 0.5f) * size);
+                v.y = __float_as_uint(__uint_as_float(pc.y) + ((float)(q >> 1) - 0.5f) * size);
+            }
+            else if (part == 3u) v.x = __float_as_uint(size);
+            else if (part == 4u) {
+                if (branch) v.x = 1u + 4u * (uint32_t)rank[c];               // children
+                if (q < 3u) v.z = e + 1u; else { v.z = pl.z; v.w = pl.w; }   // next (Quadtree.hpp:71-75)
+            }
+            else if (part == 6u) v.x = level + 1u;                           // depth
+            out[8u * e + part] = v;
+        }
+    }
+}
+
 } // namespace nbk

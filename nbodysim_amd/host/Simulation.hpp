@@ -11,8 +11,8 @@
 // `Vec2.hpp`, `Body.hpp` and `Node.hpp` (found further down the same include path), so `Vec2` keeps its
 // operators and `mag_sq` (main.cpp:108-154), `#include "Vec2.hpp"` (main.cpp:23) is a harmless repeat,
 // `std::vector<Node> SHARED_QUADTREE` (main.cpp:41) has its `Node`, and `simulation->quadtree.nodes`
-// (main.cpp:626) is this adaptor's always-empty node list (the force is a direct sum: there is no tree to
-// draw).  The UNMODIFIED main.cpp compiles against this header: INTEGRATION.md §2 gives the
+// (main.cpp:626) is this adaptor's node list: empty by default (the force is a direct sum: there is no tree to
+// draw), the tree of the step with -DNBODY_TREE=1 -DNBODY_TREE_NODES=1 (below).  The UNMODIFIED main.cpp compiles against this header: INTEGRATION.md §2 gives the
 // `g++ -std=c++20 -fsyntax-only` command that checks it.  Without the reference's headers on the path (stand-alone use, e.g.
 // sim_thread_example.cpp) minimal layout-identical `Vec2` / `Body` / `Node` are declared here instead.
 //
@@ -24,7 +24,12 @@
 // -DNBODY_COLLIDE=1, reference_params() adds NB_EXTRA_COLLIDE and step() ends with the library's restatement of
 // collide() (the pair order and the once-per-pair rule differ from the reference's spatial hash).
 // Built with -DNBODY_TREE=1, the force is the reference's own Barnes-Hut walk (NB_FORCE_TREE, theta = 1, Quake rsqrt): the
-// reference's accelerations bit for bit.  `quadtree.nodes` is not filled (the GUI's tree overlay stays empty).
+// reference's accelerations bit for bit.  `quadtree.nodes` is then still not filled (the GUI's tree overlay stays empty, and a frame
+// costs no extra call and no extra copy) unless the build also has -DNBODY_TREE_NODES=1: step() and sync() then fill it through
+// nb_tree_nodes with the tree of the last force evaluation as the reference's own `Node` records, children of a branch
+// consecutive (`nodes[children + i]`), so drawQuadtreeNode (main.cpp:394-475) draws it.  After step() that is the tree of the
+// positions before the drift, like the reference's `quadtree.nodes` after its step().  Node indices are the export's canonical
+// ones (include/nbody.h), not those of the reference's insertion order.
 #pragma once
 #include <atomic>
 #include <cmath>
@@ -68,7 +73,32 @@ struct alignas(16) Body {                                   // Body.hpp:6-17
     Body(Vec2 p, Vec2 v, float m, float r) : pos(p), vel(v), acc(Vec2::zero()), mass(m), radius(r) {}
 };
 
-struct Node {};                                             // tree node: nothing to show for a direct sum
+struct Quad {                                               // Quad.hpp: centre and edge length of a cell
+    Vec2 center;
+    float size;
+};
+
+struct Range {                                              // Node.hpp:10-29
+    size_t start = 0, end = 0;
+};
+
+struct alignas(32) Node {                                   // Node.hpp:31-53
+    struct alignas(16) {
+        Vec2 pos;
+        float mass;
+        Quad quad;
+    } data{Vec2::zero(), 0.0f, Quad{Vec2::zero(), 0.0f}};
+    size_t children = 0, next = 0;
+    Range bodies;
+    size_t depth = 0;
+    bool is_leaf() const { return children == 0; }
+    bool is_branch() const { return children != 0; }
+    bool is_empty() const { return data.mass == 0.0f; }
+};
+#endif
+
+#if defined(NBODY_TREE_NODES) && NBODY_TREE_NODES && !(defined(NBODY_TREE) && NBODY_TREE)
+#error "NBODY_TREE_NODES=1 needs NBODY_TREE=1: only a Barnes-Hut handle has a tree to export"
 #endif
 
 extern std::atomic<float> SIMULATION_DT;  // defined by the application, as in main.cpp:39
@@ -78,8 +108,18 @@ static_assert(sizeof(Body) == sizeof(nb_body) && offsetof(Body, vel) == offsetof
               offsetof(Body, acc) == offsetof(nb_body, acc) && offsetof(Body, mass) == offsetof(nb_body, mass) &&
               offsetof(Body, radius) == offsetof(nb_body, radius), "Body layout must match the C ABI (Body.hpp:6)");
 
+static_assert(sizeof(size_t) == sizeof(uint64_t) && sizeof(Node) == sizeof(nb_tree_node) && alignof(Node) == 32 &&
+              offsetof(Node, data.pos) == offsetof(nb_tree_node, pos) && offsetof(Node, data.mass) == offsetof(nb_tree_node, mass) &&
+              offsetof(Node, data.quad.center) == offsetof(nb_tree_node, center) &&
+              offsetof(Node, data.quad.size) == offsetof(nb_tree_node, size) &&
+              offsetof(Node, children) == offsetof(nb_tree_node, children) && offsetof(Node, next) == offsetof(nb_tree_node, next) &&
+              offsetof(Node, bodies.start) == offsetof(nb_tree_node, bodies_start) &&
+              offsetof(Node, bodies.end) == offsetof(nb_tree_node, bodies_end) && offsetof(Node, depth) == offsetof(nb_tree_node, depth),
+              "Node layout must match the C ABI (Node.hpp:31)");
+
 // Stand-in for the reference's `Quadtree quadtree` member (Simulation.hpp:55): the public fields its caller and a
-// harness touch.  `nodes` stays empty — main.cpp:626 copies it, main.cpp:737 draws nothing for an empty list.
+// harness touch.  `nodes` stays empty — main.cpp:626 copies it, main.cpp:737 draws nothing for an empty list — unless the
+// build has -DNBODY_TREE=1 -DNBODY_TREE_NODES=1 (fill_nodes, below).
 struct DirectSumQuadtree {
     float t_sq = 1.0f;      // Quadtree.hpp:11: theta^2 — unused by a direct sum
     float e_sq = 1.0f;      // Quadtree.hpp:12: epsilon^2 — the softening this handle was created with
@@ -139,6 +179,7 @@ public:
         const float current_dt = SIMULATION_DT.load();
         check(nb_step(sim_, current_dt, 1), "nb_step");
         check(nb_sync(sim_, reinterpret_cast<nb_body *>(bodies.data())), "nb_sync");
+        fill_nodes();
         ++frame;
     }
 
@@ -148,6 +189,8 @@ public:
     // (nb_snapshot_begin); nb_snapshot_wait then moves it into a PRIVATE vector — also while step k + 1 is running,
     // because that step was enqueued first — which is swapped with `bodies` (O(1)).  The destination of a snapshot in
     // flight is never the public vector, whose storage the caller may move at any time.  Call sync() to catch up.
+// It does NOT fill `quadtree.nodes`, with or without NBODY_TREE_NODES: `bodies` is one frame late here while the tree of the
+// handle is not, and a tree drawn over the bodies of another frame is worse than none.
     void step_overlapped()
     {
         check_size();
@@ -176,6 +219,7 @@ public:
         check_size();
         if (snapshot_in_flight_) { check(nb_snapshot_wait(sim_), "nb_snapshot_wait"); snapshot_in_flight_ = false; }
         check(nb_sync(sim_, reinterpret_cast<nb_body *>(bodies.data())), "nb_sync");
+        fill_nodes();
     }
     // After editing `bodies` in place on the host (same count).
     void upload() { check_size(); check(nb_upload(sim_, reinterpret_cast<const nb_body *>(bodies.data())), "nb_upload"); }
@@ -195,6 +239,18 @@ private:
         p.rsqrt_mode = NB_RSQRT_QUAKE;                      // own arithmetic (Quadtree.hpp:106-111): its frames bit for bit
 #endif
         return &p;
+    }
+    // -DNBODY_TREE=1 -DNBODY_TREE_NODES=1: `quadtree.nodes` = the tree of the last build (nb_tree_nodes: the count, resize, then the
+    // records written in place).  Like `bodies` the vector is the heap's and is never page-locked: the library stages the copy.
+    // Any other build: nothing, not even a call.
+    void fill_nodes()
+    {
+#if defined(NBODY_TREE_NODES) && NBODY_TREE_NODES
+        size_t count = 0;
+        check(nb_tree_nodes(sim_, nullptr, 0, &count), "nb_tree_nodes");
+        quadtree.nodes.resize(count);
+        if (count) check(nb_tree_nodes(sim_, reinterpret_cast<nb_tree_node *>(quadtree.nodes.data()), count, &count), "nb_tree_nodes");
+#endif
     }
     static void check(int rc, const char *what)
     {

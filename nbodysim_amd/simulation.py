@@ -250,6 +250,21 @@ class Simulation:
         L.check("nb_tree_stats", self._lib.nb_tree_stats(self._h, C.byref(nodes), C.byref(depth), C.byref(ovf)), self._lib)
         return {"nodes": int(nodes.value), "max_depth": int(depth.value), "overflow_steps": int(ovf.value)}
 
+    def tree_nodes(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The tree of the most recent build as the reference's ``quadtree.nodes`` (``nb_tree_nodes``; synchronises): an array of
+        ``NODE_DTYPE`` records in reference form (include/nbody.h).  The count is queried first; ``out`` (a contiguous
+        ``NODE_DTYPE`` array, e.g. a view of ``nb_host_alloc`` memory) must hold at least that many records and the view of its
+        filled part is returned; default a new array.  Empty before any build."""
+        cnt = C.c_size_t()
+        L.check("nb_tree_nodes", self._lib.nb_tree_nodes(self._h, None, 0, C.byref(cnt)), self._lib)
+        if out is None:
+            out = L.nodes_array(cnt.value)
+        elif out.dtype != L.NODE_DTYPE or out.ndim != 1 or not out.flags.c_contiguous:
+            raise TypeError("out must be a contiguous 1-D numpy array of nbodysim_amd.NODE_DTYPE (128-byte Node records)")
+        if cnt.value:
+            L.check("nb_tree_nodes", self._lib.nb_tree_nodes(self._h, out.ctypes.data, out.shape[0], C.byref(cnt)), self._lib)
+        return out[: cnt.value]
+
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
         L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)

@@ -35,6 +35,18 @@ last build, and direct / tree.
                                                ratio direct / tree.  Up to 1 048 576 bodies also |U_tree - U_direct| / |U_direct| of
                                                the initial bodies at theta 1.0, 0.7, 0.5, 0.3, without and with the quadrupole term.
 
+    python tools/tree_bench.py --nodes [case ...]                   nb_tree_nodes on the reference's arithmetic (quake, theta 1; cases default and
+                                               262144 by default).  The handle first steps for at least 2 s; five stretches give the
+                                               step and the walk (build = step - walk: the tree build, the integration and the launch
+                                               gaps).  Then, into a page-locked (nb_host_alloc) and into a pageable (numpy) destination,
+                                               FIVE times: one step, a wait, then the call under the host clock; its kernels come from
+                                               nb_profile_read (device events around the export kernels), copy = call - kernels (the
+                                               synchronisation, the DMA and, for a pageable destination, the host copy out of the
+                                               staging buffer).  nb_sync into a pageable array is timed the same way for the bytes it
+                                               moves, and a frame of the drop-in's step() (nb_step, nb_sync) without and with the two
+                                               nb_tree_nodes calls of its NBODY_TREE_NODES build (count query, then the records into a
+                                               vector that is reused).  One JSON line per case: five figures each, median and spread.
+
 With --theta the handle steps for at least 2 s, then FIVE stretches are timed; per stretch the milliseconds per step (host clock
 between two waits) and the milliseconds per walk (nb_profile_read, device events around the walk).  One JSON line per case: the
 five figures of each, their median and spread (max - min), and the walk nb_describe names.  With --leaves the line also carries
@@ -52,6 +64,7 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import nbodysim_amd as nb  # noqa: E402
+import numpy as np  # noqa: E402
 
 
 def settle(sim, dt: float, warm_s: float = 2.0) -> float:
@@ -252,7 +265,102 @@ def energy(cases, theta: float = 0.5, thetas=(1.0, 0.7, 0.5, 0.3)) -> None:
                                   "energy_ms_spread": [d["energy_ms_spread"], t["energy_ms_spread"]]}), flush=True)
 
 
+def five(f, calls: int = 5):
+    return [f() for _ in range(calls)]
+
+
+def stats_of(name: str, v, out: dict) -> None:
+    out[name] = [round(a, 4) for a in v]
+    out[name + "_median"] = round(sorted(v)[len(v) // 2], 4)
+    out[name + "_spread"] = round(max(v) - min(v), 4)
+
+
+def nodes(case: str, timed_s: float = 1.0) -> dict:
+    import ctypes as C
+    from nbodysim_amd import _lib as L
+    if case == "default":
+        bodies, kw, dt = nb.default_ics(25000), dict(eps=1.0, extras=3), 0.01
+        bodies["radius"] = 0.0
+    else:
+        bodies, kw, dt = nb.plummer_2d(int(case), 42), dict(eps=0.01), 1e-3
+    lib = nb.load()
+    out = {"case": case, "n": int(bodies.shape[0])}
+    with nb.Simulation(bodies, force="tree", rsqrt="quake", device=0, **kw) as sim:
+        est = settle(sim, dt)
+        k = max(3, min(int(timed_s / est), 5000))
+        step_ms, walk_ms = [], []
+        sim.profile(True)
+        sim.profile_read()
+        for _ in range(5):
+            t0 = time.perf_counter()
+            sim.advance(k, dt)
+            sim.wait()
+            step_ms.append((time.perf_counter() - t0) / k * 1e3)
+            ms, launches = sim.profile_read()
+            walk_ms.append(ms / launches)
+        stats_of("step_ms", step_ms, out)
+        stats_of("walk_ms", walk_ms, out)
+        out["build_ms_median"] = round(out["step_ms_median"] - out["walk_ms_median"], 4)
+        out.update(sim.tree_stats())
+        count = out["nodes"]
+        room = count + count // 4 + 4096                    # the tree grows a little while the bodies move
+        out["node_bytes"] = count * L.NODE_DTYPE.itemsize
+        ptr = lib.nb_host_alloc(room * L.NODE_DTYPE.itemsize)
+        assert ptr, L.last_error(lib)
+        pinned = np.frombuffer((C.c_uint8 * (room * L.NODE_DTYPE.itemsize)).from_address(ptr), dtype=L.NODE_DTYPE)
+        pageable = L.nodes_array(room)
+        try:
+            for name, dst in (("pinned", pinned), ("pageable", pageable)):
+                sim.tree_nodes(out=dst)                     # the first call allocates the scratch (and, pageable, the staging)
+                call, kern = [], []
+                for _ in range(5):
+                    sim.advance(1, dt)
+                    sim.wait()
+                    sim.profile_read()
+                    t0 = time.perf_counter()
+                    sim.tree_nodes(out=dst)
+                    call.append((time.perf_counter() - t0) * 1e3)
+                    kern.append(sim.profile_read()[0])
+                stats_of(f"nodes_{name}_call_ms", call, out)
+                stats_of(f"nodes_{name}_kernels_ms", kern, out)
+                stats_of(f"nodes_{name}_copy_ms", [a - b for a, b in zip(call, kern)], out)
+        finally:
+            del pinned
+            lib.nb_host_free(ptr)
+        sim.profile(False)
+
+        def timed(f):
+            def one():
+                sim.advance(1, dt)
+                sim.wait()
+                t0 = time.perf_counter()
+                f()
+                return (time.perf_counter() - t0) * 1e3
+            return one
+        sim.sync()
+        stats_of("sync_pageable_ms", five(timed(sim.sync)), out)
+        out["sync_bytes"] = int(bodies.shape[0]) * 64
+
+        def frame(with_nodes: bool):
+            def one():
+                t0 = time.perf_counter()
+                sim.step(dt)
+                if with_nodes:
+                    sim.tree_nodes(out=pageable)
+                return (time.perf_counter() - t0) * 1e3
+            return one
+        for with_nodes, name in ((False, "frame_ms"), (True, "frame_with_nodes_ms")):
+            five(frame(with_nodes))
+            v = [sum(five(frame(with_nodes), 20)) / 20 for _ in range(5)]
+            stats_of(name, v, out)
+    return out
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--nodes"]:
+        for c in sys.argv[2:] or ["default", "262144"]:
+            print(json.dumps(nodes(c)), flush=True)
+        sys.exit(0)
     if sys.argv[1:2] == ["--energy"]:
         energy(sys.argv[2:] or ["262144", "1048576", "8388608"])
         sys.exit(0)
