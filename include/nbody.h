@@ -307,6 +307,10 @@ enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered p
                                          direct energy.  No memory is added.  nb_describe appends " alpha=<value>" after "walk=...", "quad=1"
                                          and "energy=tree".  Without the bit nothing changes: same bits, same launches, same memory.
                                          Everything a NB_FLAG_TREE_LEAVES handle refuses or ignores it refuses or ignores with the bit too */
+/* every bit above: nb_create refuses any other (NB_EINVAL) */
+enum { NB_FLAGS_KNOWN = NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE |
+                        NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED |
+                        NB_FLAG_TREE_LEAVES | NB_FLAG_TREE_QUADRUPOLE | NB_FLAG_TREE_ENERGY | NB_FLAG_TREE_RELATIVE };
 
 /* ---- parameters ----------------------------------------------------------- */
 typedef struct nb_params {

@@ -6,43 +6,7 @@
 //   mass     full n            radius  full n (carried, float)
 //   vel,acc  owned block only  partial [slabs][i_count] force partial sums
 // No CPU fallback exists: every entry that computes needs a HIP device.
-#include "nbody.h"
-#include "nbody_debug.h"
-#include "nb_internal.h"
-#include "nb_kernels.hip.h"
-#include "nb_kernels3d.hip.h"
-#include "nb_collide.hip.h"
-#include "nb_tree.hip.h"
-
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <new>
-#include <type_traits>
-#include <vector>
-
-#include <unistd.h>
-
-using namespace nbk;
-
-// ---------------------------------------------------------------------------
-// errors
-// ---------------------------------------------------------------------------
-// (the thread-local error text / code and nb_params_default live in nb_host.c: plain C, shared with the CPU-only build)
-static int hip_code(hipError_t e) { return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? NB_ENOMEM : NB_EHIP; }
-
-#define HIPCHK(call)                                                                  \
-    do {                                                                              \
-        hipError_t e_ = (call);                                                       \
-        if (e_ != hipSuccess)                                                         \
-            return nb_fail(hip_code(e_), "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#include "nb_sim.hip.h"
 
 extern "C" int nb_device_count(void)
 {
@@ -51,212 +15,7 @@ extern "C" int nb_device_count(void)
     return n;
 }
 
-// ---------------------------------------------------------------------------
-// handle
-// ---------------------------------------------------------------------------
-// j_begin/j_end are virtual indices that skip [gap_begin, gap_begin + gap_len)
-struct ForceJob { uint32_t j_begin, j_end, js, slab0; int P; uint32_t i_tiles; uint32_t gap_begin, gap_len; };
-
-// How a handle computes a step: chosen once by nb_create (step_path_of) and never changed.
-enum class StepPath {
-    SYM,              // the whole system on this handle, symmetric kernel (force_sym_*)
-    SYM_SHARDED,      // symmetric, this rank's share of the pairs; the host reduce-scatters acc_full into acc_owned
-    SYM_REPLICATED,   // symmetric, this rank's share of the pairs; the host all-reduces acc_full and every rank integrates all n
-    TWO_PHASE,        // one-sided, sharded: the owned j-block first (beside the exchange), then the rest
-    ONE_SIDED,        // one-sided over job_all
-};
-
-struct nb_sim {
-    nb_params p;
-    size_t n = 0, i_begin = 0, i_count = 0;
-    int dev = 0;
-    int cus = 256;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    bool fp64 = false;
-    bool dims3 = false;        // 3-D variant: real4 {x,y,z,m} positions, real4 velocities / accelerations / slabs
-    size_t rsz = 4;            // sizeof(real)
-    size_t esz = 8;            // bytes of one position / velocity / acceleration / slab element
-
-    void *pos[2] = {nullptr, nullptr};
-    bool own_pos = true;
-    size_t pos_rows = 0;       // rows each replica holds (>= n: padded to world * ceil(n / world) for a sharded handle)
-    int cur = 0;
-    void *mass = nullptr;
-    float *radius = nullptr;
-    void *vel = nullptr, *acc = nullptr;
-    void *partial = nullptr;
-    uint32_t slabs_cap = 0;
-    BodyRec *aos_dev = nullptr;     // n records (upload) / i_count records (sync)
-    void *staging = nullptr;        // pinned host, i_count * 64 B
-    void *bounce = nullptr;         // pinned host bounce ring (BOUNCE_SLOTS x BOUNCE_SLOT_BYTES): pageable caller memory never reaches HIP
-    hipEvent_t ev_bounce[4] = {nullptr, nullptr, nullptr, nullptr};   // one per slot / per staged piece
-    double *ered_dev = nullptr;     // energy partials
-    double *pred_dev = nullptr;     // momentum partials (nb_momentum), allocated on first use
-    size_t ered_blocks = 0;
-
-    // launch geometry (per job: particles per lane and j-slices)
-    ForceJob job_all{}, job_local{}, job_remote{};
-    uint32_t slabs_all = 0, slabs_two_phase = 0;
-
-    uint64_t frame = 0;
-    float pending_dt = 0.f;
-    bool in_step = false;
-    bool mid_done = false;          // symmetric sharded protocol: nb_step_mid has run for the step in flight
-    bool acc_valid = false;         // KDK: acc holds a(x_cur)
-    bool uniform_mass = false;      // every body has the same mass: the per-pair mass multiply is hoisted
-    float um_mass = 0.f;
-    bool sym_pairs = false;         // the symmetric plan has even chunk counts (want_pairs); sym_uses_pairs decides the kernel
-    bool mass_scaled = false;       // individual masses folded into the pair geometry (MM_SCALED, nb_kernels.hip.h)
-    float *sigma = nullptr;         // m^(-1/2) per particle, for mass_scaled
-    float mass_scaling_dev = -1.0f; // what the upload-time check measured: max |a_scaled - a_general| / max |a_general| (-1: not measured)
-
-    StepPath path = StepPath::ONE_SIDED;
-    // symmetric paths (force_sym_f32): work items and its two slab sets
-    uint32_t sym_items = 0, sym_items_local = 0, sym_items_cross = 0, sym_items_late = 0;   // [local | cross | late]
-    uint32_t sym_tiles = 0, sym_rows = 0, sym_L = 0, sym_cov_late_off = 0;
-    uint32_t sym_sb = SYM_SB, sym_sb_shift = 11;   // particles per block-tile of the plan: 2048 (classic) or 512 (wave-split kernels)
-    SymItem *sym_items_dev = nullptr;          // local items first, then the cross-block items
-    uint32_t *sym_rowbase_dev = nullptr;       // 3 x tiles: first row / first late row / end row of every tile
-    uint32_t *sym_cov_begin_dev = nullptr;     // 2 x (tiles + 1): coverage-list bounds of the main and the late gather
-    SymCov *sym_cov_dev = nullptr;             // coverage entries: main lists, then (from sym_cov_late_off) the late ones
-    nb_sym_info sym_info{};
-    void *sym_slab_s = nullptr, *sym_slab_r = nullptr;       // float2 / double2 by precision
-    bool broken = false;                       // a force launch was refused by the runtime: every later step returns NB_ESTATE
-    // dynamic item tickets of the whole-system symmetric launch (sym_item_index, nb_kernels.hip.h)
-    uint32_t *sym_ticket = nullptr;            // device: one counter on a line of its own, monotonic modulo 2^32
-    uint32_t sym_ticket_base[3] = {0, 0, 0};   // what the launches so far have drawn, per launch kind (local or whole | cross | late: one counter each,
-                                               // 128 bytes apart — a sharded rank's launches may run side by side)
-    uint32_t sym_first_wave = 0;               // workgroups that keep their static item (the resident slots of the kernel variant); 0 = not yet known
-    bool sym_first_wave_uniform = false, sym_first_wave_scaled = false;   // the mass model of the instantiation it was asked for (do_upload resets it on a change)
-    // SYM_SHARDED: this rank holds the items of the tiles dealt to it.  SYM_REPLICATED (NB_FLAG_SHARD_ALLREDUCE): the handle
-    // holds this rank's share of the pairs like a sharded one, but integrates ALL n particles itself after the host has
-    // all-reduced the partial accelerations: one collective per step, every rank keeps the whole (bit-identical) state
-    void *acc_full = nullptr, *acc_owned = nullptr;     // reduce-scatter input (n) / output (i_count), (ax,ay) reals
-    bool own_acc = true;
-    // the local items run on a side stream so that their tail and the head of the cross items share the chip
-    // and the late items run there while the reduce-scatter is in flight
-    // pipelined snapshot (nb_snapshot_begin / _wait): D2H on its own stream, beside the steps that follow
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_packed = nullptr, ev_copied = nullptr;
-    nb_body *snap_out = nullptr;
-    bool snap_direct = false, snap_pending = false;
-    hipStream_t aux = nullptr;
-    bool aux_local = false;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_late = nullptr;
-    hipEvent_t ev_x[2] = {nullptr, nullptr};   // in-process exchanges: fences between the handles' streams
-    uint64_t peers_enabled = 0;                // devices whose memory this handle's device has mapped
-
-    // hard-sphere collisions (NB_EXTRA_COLLIDE, nb_collide.hip.h): nothing below is allocated when the bit is off
-    bool collide = false;
-    double coll_h = 0.0;                       // grid cell size: a little over twice the largest small radius
-    uint32_t coll_large_n = 0;                 // large bodies (tested against all n), <= COLLIDE_MAX_LARGE
-    uint32_t coll_slots = 0;                   // cell table slots (power of two >= 2n)
-    uint32_t coll_words = 0;                   // 32-body words of one large body's bitmap
-    uint64_t coll_cap = 0;                     // pair capacity
-    uint64_t coll_ovf_reported = 0;            // overflow steps already reported by a synchronising call
-    uint8_t *coll_large = nullptr;             // n flags: 1 = large body
-    uint32_t *coll_large_list = nullptr;       // COLLIDE_MAX_LARGE body indices
-    int *coll_head = nullptr, *coll_next = nullptr;
-    int2 *coll_cell = nullptr;
-    uint32_t *coll_deg = nullptr, *coll_off = nullptr, *coll_tidx = nullptr, *coll_tlist = nullptr;
-    uint32_t *coll_adj = nullptr, *coll_bits = nullptr;
-    uint64_t *coll_chunk_e = nullptr;           // the scan's per-chunk sums / prefixes (collide_scan_*)
-    uint32_t *coll_chunk_t = nullptr;
-    void *coll_spos = nullptr, *coll_svel = nullptr;   // global-memory resolution: touched bodies' state
-    uint32_t *coll_scur = nullptr;
-    uint8_t *coll_sadv = nullptr;
-    CollideStats *coll_stats = nullptr;        // device
-    CollideStats *coll_host = nullptr;         // page-locked mirror
-
-    // Barnes-Hut force (NB_FORCE_TREE, nb_tree.hip.h): nothing below is allocated for a direct-sum handle
-    bool tree = false;
-    float tree_theta2 = 1.0f;                  // theta * theta, Quadtree.hpp:18
-    bool tree_leaves = false;                  // NB_FLAG_TREE_LEAVES: leaves that are not accepted contribute
-    bool tree_quad = false;                    // NB_FLAG_TREE_QUADRUPOLE: accepted branches add their second moment
-    bool tree_energy = false;                  // NB_FLAG_TREE_ENERGY: nb_energy walks the tree (ered_dev then holds 4 x ered_blocks)
-    bool tree_rel = false;                     // NB_FLAG_TREE_RELATIVE: the walks also test m size^2 < alpha |a_prev| d^4 (nb_tree_alpha)
-    float tree_alpha = 0.005f;                 // GADGET-2's customary setting; 0 switches the test off
-    uint64_t tree_cap = 0;                     // node capacity: nodes allocated
-    uint64_t tree_ovf_reported = 0;            // failed evaluations already reported by a synchronising call
-    uint64_t *tree_k64[4] = {nullptr, nullptr, nullptr, nullptr};   // key words by body: high, low; two sort buffers
-    uint32_t *tree_v32[3] = {nullptr, nullptr, nullptr};            // body indices: identity, after the low-word sort, sorted
-    uint32_t *tree_head = nullptr;                                  // n + 1: key starts ...
-    uint64_t *tree_uidx = nullptr;                                  // ... and their prefix sum
-    uint64_t *tree_uhi = nullptr, *tree_ulo = nullptr;              // keys of the points (different positions)
-    uint32_t *tree_ufirst = nullptr;                                // first sorted position of every point
-    uint32_t *tree_cnt = nullptr;                                   // n + 2: nodes per point ...
-    uint64_t *tree_base = nullptr;                                  // ... and their prefix sum (64-bit: 440 nodes per point x 2^31 bodies)
-    float4 *tree_part = nullptr;               // bounds partials
-    TreeRoot *tree_root_dev = nullptr;
-    float4 *tree_nd = nullptr;                 // node records {com.x, com.y, mass, size^2}
-    uint32_t *tree_nx = nullptr;               // next: index + subtree size
-    uint8_t *tree_dp = nullptr;                // depth | TREE_BRANCH
-    float4 *tree_qm = nullptr;                 // second moments {xx, xy, yy, 0} per node: NB_FLAG_TREE_QUADRUPOLE handles only
-    float *tree_lo = nullptr;                  // float64 mass sum - record mass per leaf with bodies: NB_FLAG_TREE_ENERGY handles only
-    void *tree_tmp = nullptr;                  // rocprim temporary storage (sort, scan)
-    size_t tree_tmp_bytes = 0;
-    TreeStats *tree_stats = nullptr;           // device
-    TreeStats *tree_host = nullptr;            // page-locked mirror
-    // nb_tree_nodes (the export kernels of nb_tree.hip.h): nothing below exists before the first call; grown by the node count exported
-    uint64_t tree_exp_cap = 0;                 // nodes the four arrays below hold
-    uint4 *tree_exp_rec = nullptr;             // the records, 128 B per node
-    uint32_t *tree_exp_flag = nullptr;         // 1 where a pre-order node is a branch ...
-    uint64_t *tree_exp_rank = nullptr;         // ... and the prefix sum: its rank among the branches
-    uint32_t *tree_exp_idx = nullptr;          // export index of a pre-order node
-    void *tree_exp_tmp = nullptr;              // rocprim temporary storage of that scan (asked for this element count)
-    size_t tree_exp_tmp_bytes = 0;
-    void *tree_exp_stage = nullptr;            // page-locked host staging for destinations the library does not know to be page-locked
-    uint64_t tree_exp_stage_cap = 0;           // nodes it holds
-
-    // profiling
-    bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool, ev_used;
-    std::vector<uint32_t> ev_weight;           // force passes each used event pair brackets (a pipeline launch: its steps)
-    double prof_ms = 0.0;
-    uint64_t prof_launches = 0;
-};
-
-static int bind(const nb_sim *s)
-{
-    int d = -1;
-    HIPCHK(hipGetDevice(&d));
-    if (d != s->dev) HIPCHK(hipSetDevice(s->dev));
-    return NB_OK;
-}
-
-// ---------------------------------------------------------------------------
-// dispatch: run-time choices -> template arguments
-// ---------------------------------------------------------------------------
-// f(Layout<...>{}) for the handle's precision and dimensionality: the one place that maps them to types.
-template <typename F>
-static auto with_layout(const nb_sim *s, F &&f)
-{
-    if (s->dims3) return s->fp64 ? f(Layout<double, true>{}) : f(Layout<float, true>{});
-    return s->fp64 ? f(Layout<double, false>{}) : f(Layout<float, false>{});
-}
-
-// f(std::bool_constant<b>...) for the run-time flags b...
-template <typename F>
-static auto with_flags(F &&f) { return f(); }
-
-template <typename F, typename... B>
-static auto with_flags(F &&f, bool b, B... rest)
-{
-    if (b) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
-    return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
-}
-
-// f(std::integral_constant<int, P>{}) for P in {1, 2, 4}; PMAX = 2 for the fp64 kernels, which have no P = 4.
-template <int PMAX, typename F>
-static auto with_lanes(int P, F &&f)
-{
-    if constexpr (PMAX >= 4)
-        if (P == 4) return f(std::integral_constant<int, 4>{});
-    if (P == 2) return f(std::integral_constant<int, 2>{});
-    return f(std::integral_constant<int, 1>{});
-}
-
+// ---- launch geometry and step path ----
 // Launch geometry of one one-sided force job.  The kernel is VALU-bound, so what
 // matters is (a) enough independent work per lane — 2P particles per lane, P = 4 measured best — and
 // (b) enough workgroups in flight to keep 5-8 waves per SIMD issuing and to even out the tail: about
@@ -537,7 +296,7 @@ constexpr size_t SMALL_SYNC_BYTES = NB_SMALL_SYNC_BYTES;   // nb_sync: below thi
 
 static int ensure_bounce(nb_sim *s)
 {
-    if (!s->bounce) HIPCHK(hipHostMalloc(&s->bounce, BOUNCE_BYTES, hipHostMallocDefault));
+    if (!s->bounce) HIPCHK(s->pool.alloc_pinned(s->bounce, BOUNCE_BYTES));
     for (size_t k = 0; k < BOUNCE_SLOTS; ++k)
         if (!s->ev_bounce[k]) HIPCHK(hipEventCreateWithFlags(&s->ev_bounce[k], hipEventDisableTiming));
     return NB_OK;
@@ -648,18 +407,18 @@ static int plan_sym(nb_sim *s)
     std::vector<SymCov> cov(pl.cov_main);
     cov.insert(cov.end(), pl.cov_late.begin(), pl.cov_late.end());
     s->sym_cov_late_off = (uint32_t)pl.cov_main.size();
-    HIPCHK(hipMalloc((void **)&s->sym_items_dev, pl.items.size() * sizeof(SymItem)));
-    HIPCHK(hipMalloc((void **)&s->sym_rowbase_dev, bounds.size() * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->sym_cov_begin_dev, cbegin.size() * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->sym_cov_dev, (cov.size() ? cov.size() : 1) * sizeof(SymCov)));
-    HIPCHK(hipMalloc(&s->sym_slab_s, (size_t)(row ? row : 1) * pl.sb * s->esz));
-    HIPCHK(hipMalloc(&s->sym_slab_r, (size_t)(pl.slab_r_elems ? pl.slab_r_elems : 1) * s->esz));
+    HIPCHK(s->pool.alloc(s->sym_items_dev, pl.items.size()));
+    HIPCHK(s->pool.alloc(s->sym_rowbase_dev, bounds.size()));
+    HIPCHK(s->pool.alloc(s->sym_cov_begin_dev, cbegin.size()));
+    HIPCHK(s->pool.alloc(s->sym_cov_dev, cov.size() ? cov.size() : 1));
+    HIPCHK(s->pool.alloc(s->sym_slab_s, (size_t)(row ? row : 1) * pl.sb * s->esz));
+    HIPCHK(s->pool.alloc(s->sym_slab_r, (size_t)(pl.slab_r_elems ? pl.slab_r_elems : 1) * s->esz));
     int rc;
     if ((rc = copy_h2d(s, s->sym_items_dev, pl.items.data(), pl.items.size() * sizeof(SymItem)))) return rc;
     if ((rc = copy_h2d(s, s->sym_rowbase_dev, bounds.data(), bounds.size() * sizeof(uint32_t)))) return rc;
     if ((rc = copy_h2d(s, s->sym_cov_begin_dev, cbegin.data(), cbegin.size() * sizeof(uint32_t)))) return rc;
     if ((rc = copy_h2d(s, s->sym_cov_dev, cov.data(), cov.size() * sizeof(SymCov)))) return rc;
-    HIPCHK(hipMalloc((void **)&s->sym_ticket, 3 * 128));
+    HIPCHK(s->pool.alloc(s->sym_ticket, 3 * 128 / sizeof(uint32_t)));
     HIPCHK(hipMemsetAsync(s->sym_ticket, 0, 3 * 128, s->stream));
     // Side stream for the local items when they are about one wave of workgroups (P = 8 at N = 262 144: 615 items
     // on 512 resident slots, 150 us where 128 us of work is due): run concurrently, the cross items fill the CUs
@@ -675,8 +434,8 @@ static int plan_sym(nb_sim *s)
     if (split) {
         if (s->p.acc_buffers[0]) { s->acc_full = s->p.acc_buffers[0]; s->acc_owned = s->p.acc_buffers[1]; s->own_acc = false; }
         else {
-            HIPCHK(hipMalloc(&s->acc_full, (size_t)n * s->esz));
-            if (sharded) HIPCHK(hipMalloc(&s->acc_owned, s->i_count * s->esz));
+            HIPCHK(s->pool.alloc(s->acc_full, (size_t)n * s->esz));
+            if (sharded) HIPCHK(s->pool.alloc(s->acc_owned, s->i_count * s->esz));
         }
     }
     return NB_OK;
@@ -689,40 +448,17 @@ static void free_all(nb_sim *s)
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     for (auto &e : s->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto &e : s->ev_used) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    if (s->own_pos) { (void)hipFree(s->pos[0]); (void)hipFree(s->pos[1]); }
-    (void)hipFree(s->mass); (void)hipFree(s->radius); (void)hipFree(s->sigma);
-    (void)hipFree(s->vel); (void)hipFree(s->acc); (void)hipFree(s->partial);
-    (void)hipFree(s->aos_dev); (void)hipFree(s->ered_dev); (void)hipFree(s->pred_dev);
-    (void)hipFree(s->sym_items_dev); (void)hipFree(s->sym_rowbase_dev); (void)hipFree(s->sym_cov_begin_dev); (void)hipFree(s->sym_cov_dev);
-    if (s->own_acc) { (void)hipFree(s->acc_full); (void)hipFree(s->acc_owned); }
-    (void)hipFree(s->sym_slab_s); (void)hipFree(s->sym_slab_r);
-    (void)hipFree(s->sym_ticket);
-    for (void *q : {(void *)s->coll_large, (void *)s->coll_large_list, (void *)s->coll_head, (void *)s->coll_next, (void *)s->coll_cell,
-                    (void *)s->coll_deg, (void *)s->coll_off, (void *)s->coll_tidx, (void *)s->coll_tlist, (void *)s->coll_adj,
-                    (void *)s->coll_bits, (void *)s->coll_chunk_e, (void *)s->coll_chunk_t, s->coll_spos, s->coll_svel, (void *)s->coll_scur, (void *)s->coll_sadv, (void *)s->coll_stats})
-        (void)hipFree(q);
-    if (s->coll_host) (void)hipHostFree(s->coll_host);
-    for (void *q : {(void *)s->tree_k64[0], (void *)s->tree_k64[1], (void *)s->tree_k64[2], (void *)s->tree_k64[3], (void *)s->tree_v32[0],
-                    (void *)s->tree_v32[1], (void *)s->tree_v32[2], (void *)s->tree_head, (void *)s->tree_uidx, (void *)s->tree_uhi,
-                    (void *)s->tree_ulo, (void *)s->tree_ufirst, (void *)s->tree_cnt, (void *)s->tree_base, (void *)s->tree_part,
-                    (void *)s->tree_root_dev, (void *)s->tree_nd, (void *)s->tree_nx, (void *)s->tree_dp, (void *)s->tree_qm, (void *)s->tree_lo, s->tree_tmp,
-                    (void *)s->tree_stats})
-        (void)hipFree(q);
-    if (s->tree_host) (void)hipHostFree(s->tree_host);
-    for (void *q : {(void *)s->tree_exp_rec, (void *)s->tree_exp_flag, (void *)s->tree_exp_rank, (void *)s->tree_exp_idx, s->tree_exp_tmp})
-        (void)hipFree(q);
-    if (s->tree_exp_stage) (void)hipHostFree(s->tree_exp_stage);
     if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
     if (s->ev_packed) (void)hipEventDestroy(s->ev_packed);
     if (s->ev_copied) (void)hipEventDestroy(s->ev_copied);
-    if (s->staging) (void)hipHostFree(s->staging);
-    if (s->bounce) (void)hipHostFree(s->bounce);
     for (hipEvent_t e : s->ev_bounce) if (e) (void)hipEventDestroy(e);
     if (s->aux) { (void)hipStreamSynchronize(s->aux); (void)hipStreamDestroy(s->aux); }
     if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
     if (s->ev_join) (void)hipEventDestroy(s->ev_join);
     if (s->ev_late) (void)hipEventDestroy(s->ev_late);
     for (hipEvent_t e : s->ev_x) if (e) (void)hipEventDestroy(e);
+    s->pool.release_all();           // every buffer of the handle, once its three streams have drained; the caller's pos_buffers /
+                                     // acc_buffers were never in the pool
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -742,48 +478,48 @@ static int integrate_slabs(nb_sim *s, uint32_t nslabs, double dt_kick, double dt
 // passes at upload and later drifts from the origin or forms close heavy pairs is not measured again.
 // Cost: two force evaluations per upload (14 ms at N = 262 144).
 constexpr float MASS_SCALING_TOL = 2e-6f;
-static int choose_mass_scaling(nb_sim *s)
+// the two evaluations and the verdict; its temporaries live in a pool of its own, released on every way out
+static int measure_mass_scaling(nb_sim *s)
 {
     const size_t bytes = s->i_count * s->esz;
     const uint32_t n = (uint32_t)s->i_count;
+    MemPool<HipMem> tmp;
     void *saved = nullptr, *ref = nullptr;
-    uint32_t *out = nullptr;
-    int rc = NB_OK;
+    uint32_t *out = nullptr, *host = nullptr;
+    HIPCHK(tmp.alloc(saved, bytes));
+    HIPCHK(tmp.alloc(ref, bytes));
+    HIPCHK(tmp.alloc(out, 2));
+    HIPCHK(hipMemcpyAsync(saved, s->acc, bytes, hipMemcpyDeviceToDevice, s->stream));      // the uploaded acc field survives the check
+    HIPCHK(hipMemsetAsync(out, 0, 2 * sizeof(uint32_t), s->stream));
+    int r;
+    s->mass_scaled = false;
+    if ((r = launch_force(s, s->job_all)) || (r = integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0))) return r;
+    HIPCHK(hipMemcpyAsync(ref, s->acc, bytes, hipMemcpyDeviceToDevice, s->stream));
+    s->mass_scaled = true;
+    if ((r = launch_force(s, s->job_all)) || (r = integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0))) return r;
+    max_deviation_f32<<<(n + BLOCK - 1) / BLOCK, BLOCK, 0, s->stream>>>((const float2 *)s->acc, (const float2 *)ref, n, out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s->acc, saved, bytes, hipMemcpyDeviceToDevice, s->stream));
+    HIPCHK(tmp.alloc_pinned(host, 2));
+    hipError_t e = hipMemcpyAsync(host, out, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) return nb_fail(hip_code(e), "nb_upload: mass-scaling check: %s", hipGetErrorString(e));
+    float dev = 0.f, scale = 0.f;
+    memcpy(&dev, &host[0], sizeof dev);
+    memcpy(&scale, &host[1], sizeof scale);
+    const bool comparable = dev == dev && scale == scale && scale > 0.f && scale < 3.0e38f;
+    s->mass_scaling_dev = comparable ? dev / scale : HUGE_VALF;
+    s->mass_scaled = comparable && dev <= MASS_SCALING_TOL * scale;
+    return NB_OK;
+}
+
+static int choose_mass_scaling(nb_sim *s)
+{
     const bool prof = s->prof;
     s->prof = false;                  // the check's two force launches are not the caller's: keep them out of nb_profile_read
-    auto body = [&]() -> int {
-        HIPCHK(hipMalloc(&saved, bytes));
-        HIPCHK(hipMalloc(&ref, bytes));
-        HIPCHK(hipMalloc((void **)&out, 2 * sizeof(uint32_t)));
-        HIPCHK(hipMemcpyAsync(saved, s->acc, bytes, hipMemcpyDeviceToDevice, s->stream));      // the uploaded acc field survives the check
-        HIPCHK(hipMemsetAsync(out, 0, 2 * sizeof(uint32_t), s->stream));
-        int r;
-        s->mass_scaled = false;
-        if ((r = launch_force(s, s->job_all)) || (r = integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0))) return r;
-        HIPCHK(hipMemcpyAsync(ref, s->acc, bytes, hipMemcpyDeviceToDevice, s->stream));
-        s->mass_scaled = true;
-        if ((r = launch_force(s, s->job_all)) || (r = integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0))) return r;
-        max_deviation_f32<<<(n + BLOCK - 1) / BLOCK, BLOCK, 0, s->stream>>>((const float2 *)s->acc, (const float2 *)ref, n, out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(s->acc, saved, bytes, hipMemcpyDeviceToDevice, s->stream));
-        uint32_t *host = nullptr;
-        HIPCHK(hipHostMalloc((void **)&host, 2 * sizeof(uint32_t), hipHostMallocDefault));
-        hipError_t e = hipMemcpyAsync(host, out, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        float dev = 0.f, scale = 0.f;
-        memcpy(&dev, &host[0], sizeof dev);
-        memcpy(&scale, &host[1], sizeof scale);
-        (void)hipHostFree(host);
-        if (e != hipSuccess) return nb_fail(hip_code(e), "nb_upload: mass-scaling check: %s", hipGetErrorString(e));
-        const bool comparable = dev == dev && scale == scale && scale > 0.f && scale < 3.0e38f;
-        s->mass_scaling_dev = comparable ? dev / scale : HUGE_VALF;
-        s->mass_scaled = comparable && dev <= MASS_SCALING_TOL * scale;
-        return NB_OK;
-    };
-    rc = body();
+    const int rc = measure_mass_scaling(s);
     s->prof = prof;
     if (rc) s->mass_scaled = false;
-    (void)hipFree(saved); (void)hipFree(ref); (void)hipFree(out);
     s->acc_valid = false;
     return rc;
 }
@@ -800,336 +536,9 @@ static int fence_foreign_work(nb_sim *s)
     return NB_OK;
 }
 
-// ---------------------------------------------------------------------------
-// collisions (NB_EXTRA_COLLIDE): host side of nb_collide.hip.h
-// ---------------------------------------------------------------------------
-static int collide_alloc_pairs(nb_sim *s, uint64_t cap)
-{
-    (void)hipFree(s->coll_adj);
-    s->coll_adj = nullptr;
-    s->coll_cap = 0;
-    HIPCHK(hipMalloc((void **)&s->coll_adj, 2 * cap * sizeof(uint32_t)));    // every pair sits in two rows
-    s->coll_cap = cap;
-    return NB_OK;
-}
-
-// Everything the collision path needs, sized by n once (nb_create): radii never change on the device.
-static int collide_alloc(nb_sim *s)
-{
-    const size_t n = s->n;
-    uint32_t slots = 1024;
-    while (slots < 2 * n) slots <<= 1;
-    s->coll_slots = slots;
-    s->coll_words = (uint32_t)((n + 31) / 32);
-    HIPCHK(hipMalloc((void **)&s->coll_large, n));
-    HIPCHK(hipMalloc((void **)&s->coll_large_list, COLLIDE_MAX_LARGE * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->coll_head, slots * sizeof(int)));
-    HIPCHK(hipMalloc((void **)&s->coll_next, n * sizeof(int)));
-    HIPCHK(hipMalloc((void **)&s->coll_cell, n * sizeof(int2)));
-    HIPCHK(hipMalloc((void **)&s->coll_deg, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->coll_off, (n + 1) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->coll_tidx, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->coll_tlist, n * sizeof(uint32_t)));
-    const size_t chunks = (n + COLLIDE_SCAN_CHUNK - 1) / COLLIDE_SCAN_CHUNK;
-    HIPCHK(hipMalloc((void **)&s->coll_chunk_e, chunks * sizeof(uint64_t)));
-    HIPCHK(hipMalloc((void **)&s->coll_chunk_t, chunks * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->coll_bits, (size_t)COLLIDE_MAX_LARGE * s->coll_words * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&s->coll_spos, n * s->esz));
-    HIPCHK(hipMalloc(&s->coll_svel, n * s->esz));
-    HIPCHK(hipMalloc((void **)&s->coll_scur, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->coll_sadv, n));
-    HIPCHK(hipMalloc((void **)&s->coll_stats, sizeof(CollideStats)));
-    HIPCHK(hipHostMalloc((void **)&s->coll_host, sizeof(CollideStats), hipHostMallocDefault));
-    HIPCHK(hipMemsetAsync(s->coll_stats, 0, sizeof(CollideStats), s->stream));
-    memset(s->coll_host, 0, sizeof(CollideStats));
-    const uint64_t cap = std::max<uint64_t>(8 * (uint64_t)n, 65536);
-    return collide_alloc_pairs(s, cap);
-}
-
-// Size classes of the uploaded radii (magnitudes: the predicate squares r_i + r_j): r_q = the 99th percentile; bodies above
-// 2 r_q are LARGE (at most COLLIDE_MAX_LARGE, else there is no large set) and are tested against all n; the grid cell is
-// h = 2 x the largest small radius, raised by 2^-16 relative so that no pair the rounded predicate accepts (a few ulps past
-// r_i + r_j) or the rounded cell quotient places can lie beyond the neighbouring cell.
-static int collide_classify(nb_sim *s, const nb_body *in)
-{
-    const size_t n = s->n;
-    std::vector<float> r(n);
-    for (size_t i = 0; i < n; ++i) r[i] = std::fabs(in[i].radius);
-    std::vector<float> sorted(r);
-    const size_t q = (size_t)(0.99 * (double)(n - 1));
-    std::nth_element(sorted.begin(), sorted.begin() + (long)q, sorted.end(),
-                     [](float a, float b) { return a < b || (a == a && b != b); });   // NaN last
-    const float rq = sorted[q];
-    std::vector<uint8_t> large(n, 0);
-    std::vector<uint32_t> list;
-    for (size_t i = 0; i < n; ++i)
-        if (r[i] > 2.0f * rq) { large[i] = 1; list.push_back((uint32_t)i); }
-    if (list.size() > COLLIDE_MAX_LARGE) { std::fill(large.begin(), large.end(), 0); list.clear(); }
-    double rmax = 0.0;
-    for (size_t i = 0; i < n; ++i)
-        if (!large[i] && r[i] == r[i]) rmax = std::max(rmax, (double)r[i]);
-    s->coll_h = rmax > 0.0 ? 2.0 * rmax * (1.0 + 0x1p-16) : 1.0;      // radii all 0: only coincident bodies meet, any cell does
-    s->coll_large_n = (uint32_t)list.size();
-    { const int rc = copy_h2d(s, s->coll_large, large.data(), n); if (rc) return rc; }
-    if (!list.empty()) { const int rc = copy_h2d(s, s->coll_large_list, list.data(), list.size() * sizeof(uint32_t)); if (rc) return rc; }
-    return NB_OK;
-}
-
-// The collision pass of one step, on the post-drift state pos[cur] / vel (nb_collide.hip.h): `frame` is the frame it ends.
-static int launch_collide(nb_sim *s)
-{
-    const uint32_t n = (uint32_t)s->n, g = (n + BLOCK - 1) / BLOCK;
-    const uint32_t gc = std::min<uint32_t>((std::max(s->coll_slots, n) + BLOCK - 1) / BLOCK, 4096);
-    const double inv_h = std::isfinite(s->coll_h) ? 1.0 / s->coll_h : 0.0;   // an infinite radius: one cell holds everybody
-    const uint32_t mask = s->coll_slots - 1;
-    collide_clear<<<gc, BLOCK, 0, s->stream>>>(s->coll_head, s->coll_slots, s->coll_deg, n);
-    with_layout(s, [&](auto L) {
-        using real = typename decltype(L)::real;
-        using vec = typename decltype(L)::vec;
-        if constexpr (!L.dims3) {
-            vec *pos = (vec *)s->pos[s->cur], *vel = (vec *)s->vel;
-            collide_hash<vec><<<g, BLOCK, 0, s->stream>>>(pos, n, s->coll_large, inv_h, mask, s->coll_head, s->coll_next, s->coll_cell);
-            collide_rows<vec, false><<<g, BLOCK, 0, s->stream>>>(pos, s->radius, n, s->coll_large, s->coll_large_list, s->coll_large_n, mask,
-                                                                 s->coll_head, s->coll_next, s->coll_cell, s->coll_deg, nullptr, nullptr,
-                                                                 nullptr, s->coll_stats);
-            if (s->coll_large_n)
-                collide_large_bits<vec><<<dim3((s->coll_words + BLOCK - 1) / BLOCK, s->coll_large_n), BLOCK, 0, s->stream>>>(
-                    pos, s->radius, n, s->coll_large_list, s->coll_words, s->coll_bits, s->coll_deg);
-            const uint32_t chunks = (n + COLLIDE_SCAN_CHUNK - 1) / COLLIDE_SCAN_CHUNK;
-            collide_scan_blocks<<<chunks, BLOCK, 0, s->stream>>>(s->coll_deg, n, s->coll_chunk_e, s->coll_chunk_t);
-            collide_scan_top<<<1, BLOCK, 0, s->stream>>>(s->coll_chunk_e, s->coll_chunk_t, chunks, n, s->coll_off, s->coll_stats, s->coll_cap,
-                                                         s->frame);
-            collide_scan_fill<<<chunks, BLOCK, 0, s->stream>>>(s->coll_deg, n, s->coll_chunk_e, s->coll_chunk_t, s->coll_off, s->coll_tidx,
-                                                               s->coll_tlist, s->coll_stats);
-            collide_rows<vec, true><<<g, BLOCK, 0, s->stream>>>(pos, s->radius, n, s->coll_large, s->coll_large_list, s->coll_large_n, mask,
-                                                                s->coll_head, s->coll_next, s->coll_cell, nullptr, s->coll_off, s->coll_tidx,
-                                                                s->coll_adj, s->coll_stats);
-            if (s->coll_large_n)
-                collide_large_fill<<<s->coll_large_n, BLOCK, 0, s->stream>>>(s->coll_bits, s->coll_words, s->coll_large_list, s->coll_off,
-                                                                             s->coll_tidx, s->coll_adj, s->coll_stats);
-            collide_resolve<real, vec><<<1, COLLIDE_THREADS, 0, s->stream>>>(pos, vel, (const real *)s->mass, s->radius, s->coll_off,
-                                                                              s->coll_tlist, s->coll_adj, s->coll_stats, (vec *)s->coll_spos,
-                                                                              (vec *)s->coll_svel, s->coll_scur, s->coll_sadv);
-        }
-    });
-    HIPCHK(hipGetLastError());
-    return NB_OK;
-}
-
-// Reads the device record (waits for the handle's stream).  A step over capacity is reported ONCE, by the first synchronising
-// call after it: NB_ENOMEM naming the frame, the pairs needed and the capacity.
-static int collide_read(nb_sim *s)
-{
-    HIPCHK(hipMemcpyAsync(s->coll_host, s->coll_stats, sizeof(CollideStats), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return NB_OK;
-}
-
-// the report itself, from the host mirror as last read
-static int collide_report(nb_sim *s)
-{
-    if (!s->collide) return NB_OK;
-    const CollideStats &c = *s->coll_host;
-    if (c.overflow_steps <= s->coll_ovf_reported) return NB_OK;
-    const unsigned long long steps = (unsigned long long)(c.overflow_steps - s->coll_ovf_reported);
-    s->coll_ovf_reported = c.overflow_steps;
-    return nb_fail(NB_ENOMEM, "collisions: the step ending at frame %llu found %llu overlapping pairs, more than the capacity of %llu, "
-                              "and resolved none (%llu step(s) over capacity since the last report); raise it with nb_collide_capacity",
-                   (unsigned long long)c.overflow_frame, (unsigned long long)c.overflow_needed, (unsigned long long)s->coll_cap, steps);
-}
-
-static int collide_check(nb_sim *s)
-{
-    if (!s->collide) return NB_OK;
-    const int rc = collide_read(s);
-    return rc ? rc : collide_report(s);
-}
-
-// ---------------------------------------------------------------------------
-// Barnes-Hut force (NB_FORCE_TREE): host side of nb_tree.hip.h
-// ---------------------------------------------------------------------------
-static int prof_begin(nb_sim *s, std::pair<hipEvent_t, hipEvent_t> *pr, hipStream_t st);
-static int prof_end(nb_sim *s, const std::pair<hipEvent_t, hipEvent_t> &pr, hipStream_t st, uint32_t passes);
-
-// Node capacity: 16 n + 4096.  Measured (DESIGN.md "Barnes-Hut force"): the reference's default bodies need 2.8 n nodes, Plummer
-// spheres of 1 048 576 and 8 388 608 bodies 2.9 n; a pair of bodies much closer than its neighbours adds four nodes per level it
-// takes to part them (the 256 isolated touching pairs of tests/golden/collide_isolated_ic.npy: 10.2 n).
-static int tree_alloc(nb_sim *s)
-{
-    const size_t n = s->n;
-    s->tree_cap = std::min<uint64_t>(16 * (uint64_t)n + 4096, 0xfffffff0u);
-    for (auto &q : s->tree_k64) HIPCHK(hipMalloc((void **)&q, n * sizeof(uint64_t)));
-    for (auto &q : s->tree_v32) HIPCHK(hipMalloc((void **)&q, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_head, (n + 1) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_uidx, (n + 1) * sizeof(uint64_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_uhi, n * sizeof(uint64_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_ulo, n * sizeof(uint64_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_ufirst, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_cnt, (n + 2) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_base, (n + 2) * sizeof(uint64_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_part, TREE_BOUNDS_BLOCKS * sizeof(float4)));
-    HIPCHK(hipMalloc((void **)&s->tree_root_dev, sizeof(TreeRoot)));
-    HIPCHK(hipMalloc((void **)&s->tree_nd, s->tree_cap * sizeof(float4)));
-    HIPCHK(hipMalloc((void **)&s->tree_nx, s->tree_cap * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_dp, s->tree_cap));
-    if (s->tree_quad) {     // +16 B per node (+256 B per body); zeroed once: the build writes every record a walk can read
-        HIPCHK(hipMalloc((void **)&s->tree_qm, s->tree_cap * sizeof(float4)));
-        HIPCHK(hipMemsetAsync(s->tree_qm, 0, s->tree_cap * sizeof(float4), s->stream));
-    }
-    if (s->tree_energy) HIPCHK(hipMalloc((void **)&s->tree_lo, s->tree_cap * sizeof(float)));   // +4 B per node; written per build
-    size_t sort_bytes = 0, scan_bytes = 0;
-    HIPCHK(nb_tree_sort_pairs(nullptr, sort_bytes, s->tree_k64[0], s->tree_k64[2], s->tree_v32[0], s->tree_v32[1], n, s->stream));
-    HIPCHK(nb_tree_scan(nullptr, scan_bytes, s->tree_cnt, s->tree_base, n + 2, s->stream));
-    s->tree_tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 256);
-    HIPCHK(hipMalloc(&s->tree_tmp, s->tree_tmp_bytes));
-    HIPCHK(hipMalloc((void **)&s->tree_stats, sizeof(TreeStats)));
-    HIPCHK(hipHostMalloc((void **)&s->tree_host, sizeof(TreeStats), hipHostMallocDefault));
-    HIPCHK(hipMemsetAsync(s->tree_stats, 0, sizeof(TreeStats), s->stream));
-    memset(s->tree_host, 0, sizeof(TreeStats));
-    return NB_OK;
-}
-
-// The walk of a NB_FLAG_TREE_LEAVES handle: the wave-uniform one with the hardware rsqrt, the per-lane one (the form the CPU
-// model restates bit for bit) with the Quake rsqrt.
-static bool tree_walk_is_group(const nb_sim *s) { return s->tree_leaves && s->p.rsqrt_mode != NB_RSQRT_QUAKE; }
-
-// NB_FLAG_TREE_RELATIVE with alpha != 0.  alpha = 0 switches the test off: the handle then runs the launches of the handle without
-// the flag, and so produces its bits.
-static bool tree_rel_active(const nb_sim *s) { return s->tree_rel && s->tree_alpha != 0.0f; }
-
-// The tree of pos[cur] (nb_tree.hip.h has the pipeline): bounds ... tree_com.  A force evaluation and, on a NB_FLAG_TREE_ENERGY
-// handle, nb_energy start with it.
-static int launch_tree_build(nb_sim *s)
-{
-    const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u, g2 = (n + 2u + 255u) / 256u;
-    const float2 *pos = (const float2 *)s->pos[s->cur];
-    const float *mass = (const float *)s->mass;
-    uint64_t *khi = s->tree_k64[0], *klo = s->tree_k64[1], *ka = s->tree_k64[2], *kb = s->tree_k64[3];
-    uint32_t *v0 = s->tree_v32[0], *v1 = s->tree_v32[1], *v2 = s->tree_v32[2];
-    TreeStats *st = s->tree_stats;
-    size_t tmp = s->tree_tmp_bytes;
-    tree_bounds<<<std::min(g, TREE_BOUNDS_BLOCKS), 256, 0, s->stream>>>(pos, n, s->tree_part);
-    tree_root<<<1, 256, 0, s->stream>>>(s->tree_part, std::min(g, TREE_BOUNDS_BLOCKS), s->tree_root_dev, st);
-    tree_keys<<<g, 256, 0, s->stream>>>(pos, mass, n, s->tree_root_dev, khi, klo, v0, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(nb_tree_sort_pairs(s->tree_tmp, tmp, klo, ka, v0, v1, n, s->stream));          // by the low word ...
-    tree_gather_hi<<<g, 256, 0, s->stream>>>(khi, v1, n, kb);
-    HIPCHK(nb_tree_sort_pairs(s->tree_tmp, tmp, kb, ka, v1, v2, n, s->stream));           // ... then, stable, by the high one
-    tree_heads<<<g2, 256, 0, s->stream>>>(ka, klo, v2, pos, n, s->tree_head, st, s->frame);
-    HIPCHK(hipGetLastError());
-    HIPCHK(nb_tree_scan(s->tree_tmp, tmp, s->tree_head, s->tree_uidx, (size_t)n + 1, s->stream));
-    tree_points<<<g2, 256, 0, s->stream>>>(ka, klo, v2, s->tree_head, s->tree_uidx, n, s->tree_uhi, s->tree_ulo, s->tree_ufirst, st);
-    tree_count<<<g2, 256, 0, s->stream>>>(s->tree_uhi, s->tree_ulo, n, s->tree_cnt, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(nb_tree_scan(s->tree_tmp, tmp, s->tree_cnt, s->tree_base, (size_t)n + 2, s->stream));
-    tree_emit<<<g2, 256, 0, s->stream>>>(s->tree_uhi, s->tree_ulo, s->tree_ufirst, v2, pos, mass, s->tree_base, n, s->tree_root_dev, s->tree_cap,
-                                         s->tree_nd, s->tree_nx, s->tree_dp, st, s->frame);
-    const uint32_t gc = (uint32_t)std::min<uint64_t>((s->tree_cap + 255u) / 256u, 8u * (uint32_t)s->cus);
-    with_flags([&](auto quad) {
-        for (int level = TREE_DEPTH_CAP - 1; level >= 0; --level)
-            tree_com<quad><<<gc, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, (uint32_t)level, st, s->tree_qm);
-    }, s->tree_quad);
-    HIPCHK(hipGetLastError());
-    return NB_OK;
-}
-
-// One force evaluation at pos[cur] into acc[]: the build, then the walk.  The walk is "the force kernel" of nb_profile_read.
-static int launch_tree_force(nb_sim *s)
-{
-    { const int rc = launch_tree_build(s); if (rc) return rc; }
-    const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u;
-    const float2 *pos = (const float2 *)s->pos[s->cur];
-    uint32_t *v2 = s->tree_v32[2];
-    TreeStats *st = s->tree_stats;
-    std::pair<hipEvent_t, hipEvent_t> pr;
-    if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
-    const float eps2 = s->p.eps * s->p.eps, alpha = s->tree_alpha;
-    const float4 *qm = s->tree_qm;
-    const bool quake = s->p.rsqrt_mode == NB_RSQRT_QUAKE;
-    auto lanes = [&](auto kernel) {         // a per-lane walk
-        kernel<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st, qm, alpha);
-    };
-    auto windows = [&](auto kernel) {       // tree_walk_group and tree_walk_alone: the same with the three arrays of tree_lane_alone
-        kernel<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, n, eps2, s->tree_theta2, (float2 *)s->acc, st,
-                                         s->tree_head, s->tree_uidx, s->tree_ufirst, qm, alpha);
-    };
-    if (tree_walk_is_group(s)) {            // the group walk, then the few lanes that left it (nb_tree.hip.h): one "force kernel" interval
-        with_flags([&](auto quad, auto rel) {
-            windows(tree_walk_group<quad, rel>);
-            windows(tree_walk_alone<quad, rel>);
-        }, s->tree_quad, tree_rel_active(s));
-    } else if (s->tree_leaves) {            // per lane (the Quake rsqrt: tree_walk_is_group): QUAD and REL exist with RSQ_QUAKE only
-        with_flags([&](auto q, auto quad, auto rel) {
-            if constexpr (q || !(quad || rel)) lanes(tree_walk<q ? RSQ_QUAKE : RSQ_EXACT, true, quad, rel>);
-        }, quake, s->tree_quad, tree_rel_active(s));
-    } else {                                // the reference's walk
-        with_flags([&](auto q) { lanes(tree_walk<q ? RSQ_QUAKE : RSQ_EXACT, false, false, false>); }, quake);
-    }
-    HIPCHK(hipGetLastError());
-    if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
-    return NB_OK;
-}
-
-// nb_energy of a NB_FLAG_TREE_ENERGY handle: the tree of the current positions, the float64 mass residuals of its leaves, then the
-// potential walk (nb_tree.hip.h): the
-// windows into partials [0, g) (K) and [g, 2g) (U), the lanes that left them into [2g, 3g) and [3g, 4g).  Touches neither acc[]
-// nor the state; the tree arrays are this build's afterwards.
-static int launch_tree_potential(nb_sim *s)
-{
-    { const int rc = launch_tree_build(s); if (rc) return rc; }
-    const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u;
-    const float2 *pos = (const float2 *)s->pos[s->cur], *vel = (const float2 *)s->vel;
-    const float *mass = (const float *)s->mass;
-    const uint32_t *v2 = s->tree_v32[2];
-    const TreeStats *st = s->tree_stats;
-    const double eps2 = (double)s->p.eps * (double)s->p.eps;
-    double *e = s->ered_dev;
-    const float4 *qm = s->tree_qm;
-    const float *lo = s->tree_lo;
-    tree_leaf_residual<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_base, s->tree_ufirst, v2, mass, n, st, s->tree_lo);
-    const float2 *aprev = (const float2 *)s->acc;           // REL: the predicate of a force evaluation issued now: acc[] of this moment, read only
-    with_flags([&](auto quad, auto rel) {
-        tree_potential_group<quad, rel><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st,
-                                                                  s->tree_head, s->tree_uidx, s->tree_ufirst, e, e + g, lo, qm, aprev, s->tree_alpha);
-        tree_potential_alone<quad, rel><<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, v2, pos, vel, mass, n, eps2, s->tree_theta2, st,
-                                                                  s->tree_head, s->tree_uidx, s->tree_ufirst, e + 2 * (size_t)g,
-                                                                  e + 3 * (size_t)g, lo, qm, aprev, s->tree_alpha);
-    }, s->tree_quad, tree_rel_active(s));
-    HIPCHK(hipGetLastError());
-    return NB_OK;
-}
-
-// acc[] of the tree walk -> kick, drift (or acc only): the reference-order form with the Quake rsqrt, the fused one otherwise
-static int launch_tree_integrate(nb_sim *s, double dt_kick, double dt_drift, int flags)
-{
-    const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u;
-    using L2 = Layout<float, false>;
-    with_flags([&](auto strict) {
-        tree_integrate<L2, strict><<<g, 256, 0, s->stream>>>((const float2 *)s->pos[s->cur], (float2 *)s->pos[s->cur ^ 1], (float2 *)s->vel,
-                                                              (float2 *)s->acc, n, (float)dt_kick, (float)dt_drift, s->p.extras, flags, s->tree_stats);
-    }, s->p.rsqrt_mode == NB_RSQRT_QUAKE);
-    HIPCHK(hipGetLastError());
-    return NB_OK;
-}
-
-// A failed build (node capacity, depth cap) is reported ONCE, by the first synchronising call after it, like a collision overflow.
-static int tree_check(nb_sim *s)
-{
-    if (!s->tree) return NB_OK;
-    HIPCHK(hipMemcpyAsync(s->tree_host, s->tree_stats, sizeof(TreeStats), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    const TreeStats &t = *s->tree_host;
-    if (t.overflow_steps <= s->tree_ovf_reported) return NB_OK;
-    const unsigned long long steps = (unsigned long long)(t.overflow_steps - s->tree_ovf_reported);
-    s->tree_ovf_reported = t.overflow_steps;
-    if (t.overflow_kind == 1)
-        return nb_fail(NB_ENOMEM, "tree: the force evaluation at frame %llu needed %llu nodes, more than the capacity of %llu; nothing was "
-                                  "integrated (%llu evaluation(s) failed since the last report)",
-                       (unsigned long long)t.overflow_frame, (unsigned long long)t.overflow_needed, (unsigned long long)s->tree_cap, steps);
-    return nb_fail(NB_ENOMEM, "tree: at frame %llu two different positions (sorted position %llu) are not separated within %d levels; nothing "
-                              "was integrated (%llu evaluation(s) failed since the last report)",
-                   (unsigned long long)t.overflow_frame, (unsigned long long)t.overflow_needed, TREE_DEPTH_CAP, steps);
-}
+// ---- the two subsystems' host code (it moves its data with copy_h2d / copy_d2h above) ----
+#include "nb_collide_host.hip.h"
+#include "nb_tree_host.hip.h"
 
 // what every synchronising call reports once: a collision step over capacity, a failed tree build
 static int step_check(nb_sim *s)
@@ -1189,7 +598,7 @@ static int do_upload(nb_sim *s, const nb_body *in)
     });
     HIPCHK(hipGetLastError());
     if (forced_scaling || auto_scaling) {
-        if (!s->sigma) HIPCHK(hipMalloc((void **)&s->sigma, s->n * sizeof(float)));
+        if (!s->sigma) HIPCHK(s->pool.alloc(s->sigma, s->n));
         mass_sigma<<<g, BLOCK, 0, s->stream>>>((const float *)s->mass, s->sigma, n);
         HIPCHK(hipGetLastError());
     }
@@ -1228,7 +637,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
         nb_set_error("nb_create: quake rsqrt / sequential order are fp32 (reference arithmetic) modes");
         return nullptr;
     }
-    if (p.flags & ~(NB_FLAG_NO_SYMMETRY | NB_FLAG_NO_UNIFORM_MASS | NB_FLAG_NO_GUIDED_TAIL | NB_FLAG_SHARD_ALLREDUCE | NB_FLAG_SHARD_SINGLE | NB_FLAG_MASS_SCALING | NB_FLAG_NO_MASS_SCALING | NB_FLAG_STATIC_ITEMS | NB_FLAG_MASS_SCALING_MEASURED | NB_FLAG_TREE_LEAVES | NB_FLAG_TREE_QUADRUPOLE | NB_FLAG_TREE_ENERGY | NB_FLAG_TREE_RELATIVE)) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
+    if (p.flags & ~NB_FLAGS_KNOWN) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
     if (p.extras & ~(NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY | NB_EXTRA_COLLIDE)) { nb_set_error("nb_create: unknown bits in extras 0x%x", (unsigned)p.extras); return nullptr; }
     if (p.extras & NB_EXTRA_COLLIDE) {
         const char *why = p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
@@ -1240,27 +649,23 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     }
     if (p.force != NB_FORCE_DIRECT && p.force != NB_FORCE_TREE) { nb_set_error("nb_create: bad force %d", p.force); return nullptr; }
     if (!(p.theta >= 0.0f) || !std::isfinite(p.theta)) { nb_set_error("nb_create: theta must be >= 0 and finite"); return nullptr; }
-    if ((p.flags & NB_FLAG_TREE_RELATIVE) && (p.force != NB_FORCE_TREE || !(p.flags & NB_FLAG_TREE_LEAVES))) {
-        nb_set_error("nb_create: NB_FLAG_TREE_RELATIVE %s: the flag adds an acceleration-relative opening test to the walks of the "
-                     "convergent Barnes-Hut force (NB_FORCE_TREE with NB_FLAG_TREE_LEAVES)",
-                     p.force == NB_FORCE_TREE ? "without NB_FLAG_TREE_LEAVES" : (p.flags & NB_FLAG_TREE_LEAVES) ? "with NB_FORCE_DIRECT"
-                                                : "with NB_FORCE_DIRECT and without NB_FLAG_TREE_LEAVES");
-        return nullptr;
-    }
-    if ((p.flags & NB_FLAG_TREE_ENERGY) && (p.force != NB_FORCE_TREE || !(p.flags & NB_FLAG_TREE_LEAVES))) {
-        nb_set_error("nb_create: NB_FLAG_TREE_ENERGY %s: the flag makes nb_energy walk the tree of the convergent Barnes-Hut force "
-                     "(NB_FORCE_TREE with NB_FLAG_TREE_LEAVES; without the leaves a walk has no near field and no meaningful potential)",
-                     p.force == NB_FORCE_TREE ? "without NB_FLAG_TREE_LEAVES" : (p.flags & NB_FLAG_TREE_LEAVES) ? "with NB_FORCE_DIRECT"
-                                                : "with NB_FORCE_DIRECT and without NB_FLAG_TREE_LEAVES");
-        return nullptr;
-    }
-    if ((p.flags & NB_FLAG_TREE_QUADRUPOLE) && (p.force != NB_FORCE_TREE || !(p.flags & NB_FLAG_TREE_LEAVES))) {
-        nb_set_error("nb_create: NB_FLAG_TREE_QUADRUPOLE %s: the flag adds the second moment of an accepted cell to the convergent Barnes-Hut "
-                     "force (NB_FORCE_TREE with NB_FLAG_TREE_LEAVES)",
-                     p.force == NB_FORCE_TREE ? "without NB_FLAG_TREE_LEAVES" : (p.flags & NB_FLAG_TREE_LEAVES) ? "with NB_FORCE_DIRECT"
-                                                : "with NB_FORCE_DIRECT and without NB_FLAG_TREE_LEAVES");
-        return nullptr;
-    }
+    // flags of the convergent Barnes-Hut force: each needs NB_FORCE_TREE with NB_FLAG_TREE_LEAVES (checked in this order)
+    static const struct { int32_t flag; const char *name, *sentence; } tree_flags[3] = {
+        {NB_FLAG_TREE_RELATIVE, "NB_FLAG_TREE_RELATIVE",
+         "the flag adds an acceleration-relative opening test to the walks of the convergent Barnes-Hut force (NB_FORCE_TREE with NB_FLAG_TREE_LEAVES)"},
+        {NB_FLAG_TREE_ENERGY, "NB_FLAG_TREE_ENERGY",
+         "the flag makes nb_energy walk the tree of the convergent Barnes-Hut force (NB_FORCE_TREE with NB_FLAG_TREE_LEAVES; without the leaves "
+         "a walk has no near field and no meaningful potential)"},
+        {NB_FLAG_TREE_QUADRUPOLE, "NB_FLAG_TREE_QUADRUPOLE",
+         "the flag adds the second moment of an accepted cell to the convergent Barnes-Hut force (NB_FORCE_TREE with NB_FLAG_TREE_LEAVES)"},
+    };
+    for (const auto &f : tree_flags)
+        if ((p.flags & f.flag) && (p.force != NB_FORCE_TREE || !(p.flags & NB_FLAG_TREE_LEAVES))) {
+            nb_set_error("nb_create: %s %s: %s", f.name,
+                         p.force == NB_FORCE_TREE ? "without NB_FLAG_TREE_LEAVES" : (p.flags & NB_FLAG_TREE_LEAVES) ? "with NB_FORCE_DIRECT"
+                                                    : "with NB_FORCE_DIRECT and without NB_FLAG_TREE_LEAVES", f.sentence);
+            return nullptr;
+        }
     if ((p.flags & NB_FLAG_TREE_LEAVES) && p.force != NB_FORCE_TREE) {
         nb_set_error("nb_create: NB_FLAG_TREE_LEAVES with NB_FORCE_DIRECT: the flag selects a walk of the Barnes-Hut force (NB_FORCE_TREE)");
         return nullptr;
@@ -1339,8 +744,8 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
         // a sharded handle's replicas hold world * ceil(n / world) rows: an all-gather over ragged blocks moves equal counts
         const size_t w = p.shard_world > 1 ? (size_t)p.shard_world : 1;
         s->pos_rows = w * ((n + w - 1) / w);
-        if ((e = hipMalloc(&s->pos[0], s->pos_rows * r2)) != hipSuccess) return fail("hipMalloc pos", e);
-        if ((e = hipMalloc(&s->pos[1], s->pos_rows * r2)) != hipSuccess) return fail("hipMalloc pos", e);
+        if ((e = s->pool.alloc(s->pos[0], s->pos_rows * r2)) != hipSuccess) return fail("allocating pos", e);
+        if ((e = s->pool.alloc(s->pos[1], s->pos_rows * r2)) != hipSuccess) return fail("allocating pos", e);
         if (s->pos_rows > n) {          // the padding rows travel with the last block: keep them defined
             if ((e = hipMemsetAsync((char *)s->pos[0] + n * r2, 0, (s->pos_rows - n) * r2, s->stream)) != hipSuccess) return fail("hipMemset pos", e);
             if ((e = hipMemsetAsync((char *)s->pos[1] + n * r2, 0, (s->pos_rows - n) * r2, s->stream)) != hipSuccess) return fail("hipMemset pos", e);
@@ -1348,26 +753,24 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     }
     s->slabs_cap = s->slabs_all > s->slabs_two_phase ? s->slabs_all : s->slabs_two_phase;
     s->tree = p.force == NB_FORCE_TREE;
-    s->tree_theta2 = p.theta * p.theta;
-    s->tree_leaves = s->tree && (p.flags & NB_FLAG_TREE_LEAVES) != 0;
-    s->tree_quad = s->tree_leaves && (p.flags & NB_FLAG_TREE_QUADRUPOLE) != 0;
-    s->tree_energy = s->tree_leaves && (p.flags & NB_FLAG_TREE_ENERGY) != 0;
-    s->tree_rel = s->tree_leaves && (p.flags & NB_FLAG_TREE_RELATIVE) != 0;
-    if ((e = hipMalloc(&s->mass, n * s->rsz)) != hipSuccess) return fail("hipMalloc mass", e);
-    if ((e = hipMalloc((void **)&s->radius, n * sizeof(float))) != hipSuccess) return fail("hipMalloc radius", e);
-    if ((e = hipMalloc(&s->vel, s->i_count * r2)) != hipSuccess) return fail("hipMalloc vel", e);
-    if ((e = hipMalloc(&s->acc, s->i_count * r2)) != hipSuccess) return fail("hipMalloc acc", e);
+    s->bh.theta2 = p.theta * p.theta;
+    s->bh.leaves = s->tree && (p.flags & NB_FLAG_TREE_LEAVES) != 0;
+    s->bh.quad = s->bh.leaves && (p.flags & NB_FLAG_TREE_QUADRUPOLE) != 0;
+    s->bh.energy = s->bh.leaves && (p.flags & NB_FLAG_TREE_ENERGY) != 0;
+    s->bh.rel = s->bh.leaves && (p.flags & NB_FLAG_TREE_RELATIVE) != 0;
+    if ((e = s->pool.alloc(s->mass, n * s->rsz)) != hipSuccess) return fail("allocating mass", e);
+    if ((e = s->pool.alloc(s->radius, n)) != hipSuccess) return fail("allocating radius", e);
+    if ((e = s->pool.alloc(s->vel, s->i_count * r2)) != hipSuccess) return fail("allocating vel", e);
+    if ((e = s->pool.alloc(s->acc, s->i_count * r2)) != hipSuccess) return fail("allocating acc", e);
     // (a tree handle has no one-sided partials: its walk writes acc[] itself)
-    if ((e = hipMalloc(&s->partial, s->tree ? r2 : (size_t)s->slabs_cap * s->i_count * r2)) != hipSuccess) return fail("hipMalloc partial", e);
-    if ((e = hipMalloc((void **)&s->aos_dev, n * sizeof(nb_body))) != hipSuccess) return fail("hipMalloc aos", e);
+    if ((e = s->pool.alloc(s->partial, s->tree ? r2 : (size_t)s->slabs_cap * s->i_count * r2)) != hipSuccess) return fail("allocating partial", e);
+    if ((e = s->pool.alloc(s->aos_dev, n)) != hipSuccess) return fail("allocating aos", e);
     s->ered_blocks = (s->i_count + BLOCK - 1) / BLOCK;
-    if ((e = hipMalloc((void **)&s->ered_dev, (s->tree_energy ? 4 : 2) * s->ered_blocks * sizeof(double))) != hipSuccess) return fail("hipMalloc energy", e);
+    if ((e = s->pool.alloc(s->ered_dev, (s->bh.energy ? 4 : 2) * s->ered_blocks)) != hipSuccess) return fail("allocating energy", e);
 
-    if (symmetric(s) && plan_sym(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
     s->collide = (p.extras & NB_EXTRA_COLLIDE) != 0;
-    if (s->collide && collide_alloc(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
-    if (s->tree && tree_alloc(s) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
-    if (do_upload(s, init) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }
+    if ((symmetric(s) && plan_sym(s) != NB_OK) || (s->collide && collide_alloc(s) != NB_OK) || (s->tree && tree_alloc(s) != NB_OK) ||
+        do_upload(s, init) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }     // (nb_fail has said why)
     return s;
 }
 
@@ -1384,7 +787,7 @@ extern "C" int nb_upload(nb_sim *s, const nb_body *in)
 // ---------------------------------------------------------------------------
 // profiling events
 // ---------------------------------------------------------------------------
-static int prof_begin(nb_sim *s, std::pair<hipEvent_t, hipEvent_t> *pr, hipStream_t st = nullptr)
+static int prof_begin(nb_sim *s, std::pair<hipEvent_t, hipEvent_t> *pr, hipStream_t st)
 {
     if (s->ev_pool.empty()) {
         hipEvent_t a, b;
@@ -1398,7 +801,7 @@ static int prof_begin(nb_sim *s, std::pair<hipEvent_t, hipEvent_t> *pr, hipStrea
     return NB_OK;
 }
 
-static int prof_end(nb_sim *s, const std::pair<hipEvent_t, hipEvent_t> &pr, hipStream_t st = nullptr, uint32_t passes = 1)
+static int prof_end(nb_sim *s, const std::pair<hipEvent_t, hipEvent_t> &pr, hipStream_t st, uint32_t passes)
 {
     HIPCHK(hipEventRecord(pr.second, st ? st : s->stream));
     s->ev_used.push_back(pr);
@@ -1814,7 +1217,7 @@ extern "C" int nb_wait(nb_sim *s)
 // ---------------------------------------------------------------------------
 static int ensure_staging(nb_sim *s)
 {
-    if (!s->staging) HIPCHK(hipHostMalloc(&s->staging, s->i_count * sizeof(nb_body), hipHostMallocDefault));
+    if (!s->staging) HIPCHK(s->pool.alloc_pinned(s->staging, s->i_count * sizeof(nb_body)));
     return NB_OK;
 }
 
@@ -1936,7 +1339,7 @@ extern "C" int nb_snapshot_begin(nb_sim *s, nb_body *out)
     // aos_dev is free again: the previous snapshot was waited for, and nb_sync / nb_upload synchronise before returning
     int rc = launch_pack(s);
     if (rc) return rc;
-    if (s->collide) HIPCHK(hipMemcpyAsync(s->coll_host, s->coll_stats, sizeof(CollideStats), hipMemcpyDeviceToHost, s->stream));
+    if (s->collide) HIPCHK(hipMemcpyAsync(s->coll.host, s->coll.stats, sizeof(CollideStats), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipEventRecord(s->ev_packed, s->stream));
     HIPCHK(hipStreamWaitEvent(s->copy_stream, s->ev_packed, 0));
     HIPCHK(hipMemcpyAsync(s->snap_direct ? (void *)out : s->staging, s->aos_dev, s->i_count * sizeof(nb_body), hipMemcpyDeviceToHost, s->copy_stream));
@@ -2008,32 +1411,26 @@ extern "C" int nb_energy(nb_sim *s, double *kinetic, double *potential)
     if (!s || !kinetic || !potential) return nb_fail(NB_EINVAL, "nb_energy: NULL argument");
     if (bind(s)) return NB_EHIP;
     { const int rc = step_check(s); if (rc) return rc; }
-    const uint32_t g = (uint32_t)s->ered_blocks;
-    if (s->tree_energy) {       // O(n log n): the tree of the current positions and its potential walk; a failed build is reported by THIS call
+    const uint32_t g = (uint32_t)s->ered_blocks, sets = s->bh.energy ? 2u : 1u;     // sets of partials [K (g) | U (g)] the kernels leave
+    if (s->bh.energy) {       // O(n log n): the tree of the current positions and its potential walk; a failed build is reported by THIS call
         { const int rc = launch_tree_potential(s); if (rc) return rc; }
         { const int rc = tree_check(s); if (rc) return rc; }
-        std::vector<double> h(4 * (size_t)g);
-        { const int rc = copy_d2h(s, h.data(), s->ered_dev, h.size() * sizeof(double)); if (rc) return rc; }
-        double K = 0.0, U = 0.0;
-        for (uint32_t q = 0; q < 2; ++q)
-            for (uint32_t b = 0; b < g; ++b) { K += h[2 * (size_t)q * g + b]; U += h[(2 * (size_t)q + 1) * g + b]; }
-        *kinetic = K;
-        *potential = U;
-        return NB_OK;
+    } else {
+        const double eps2 = (double)s->p.eps * (double)s->p.eps;
+        with_layout(s, [&](auto L) {
+            using real = typename decltype(L)::real;
+            using vec = typename decltype(L)::vec;
+            const vec *pos = (const vec *)s->pos[s->cur], *vel = (const vec *)s->vel;
+            energy_partials<decltype(L)><<<g, BLOCK, 0, s->stream>>>(pos, (const real *)s->mass, vel, (uint32_t)s->n, (uint32_t)s->i_begin,
+                                                                     (uint32_t)s->i_count, eps2, s->ered_dev, s->ered_dev + g);
+        });
+        HIPCHK(hipGetLastError());
     }
-    const double eps2 = (double)s->p.eps * (double)s->p.eps;
-    with_layout(s, [&](auto L) {
-        using real = typename decltype(L)::real;
-        using vec = typename decltype(L)::vec;
-        const vec *pos = (const vec *)s->pos[s->cur], *vel = (const vec *)s->vel;
-        energy_partials<decltype(L)><<<g, BLOCK, 0, s->stream>>>(pos, (const real *)s->mass, vel, (uint32_t)s->n, (uint32_t)s->i_begin,
-                                                                 (uint32_t)s->i_count, eps2, s->ered_dev, s->ered_dev + g);
-    });
-    HIPCHK(hipGetLastError());
-    std::vector<double> h(2 * (size_t)g);
+    std::vector<double> h(2 * (size_t)sets * g);
     { const int rc = copy_d2h(s, h.data(), s->ered_dev, h.size() * sizeof(double)); if (rc) return rc; }
     double K = 0.0, U = 0.0;
-    for (uint32_t b = 0; b < g; ++b) { K += h[b]; U += h[g + b]; }
+    for (uint32_t q = 0; q < sets; ++q)
+        for (uint32_t b = 0; b < g; ++b) { K += h[2 * (size_t)q * g + b]; U += h[(2 * (size_t)q + 1) * g + b]; }
     *kinetic = K;
     *potential = U;
     return NB_OK;
@@ -2045,7 +1442,7 @@ extern "C" int nb_momentum(nb_sim *s, double *p_xyz, double *l_z)
     if (bind(s)) return NB_EHIP;
     { const int rc = step_check(s); if (rc) return rc; }
     const uint32_t g = (uint32_t)s->ered_blocks;
-    if (!s->pred_dev) HIPCHK(hipMalloc((void **)&s->pred_dev, 4 * (size_t)g * sizeof(double)));
+    if (!s->pred_dev) HIPCHK(s->pool.alloc(s->pred_dev, 4 * (size_t)g));
     with_layout(s, [&](auto L) {
         using real = typename decltype(L)::real;
         using vec = typename decltype(L)::vec;
@@ -2061,126 +1458,6 @@ extern "C" int nb_momentum(nb_sim *s, double *p_xyz, double *l_z)
         for (uint32_t b = 0; b < g; ++b) acc[c] += h[(size_t)c * g + b];
     p_xyz[0] = acc[0]; p_xyz[1] = acc[1]; p_xyz[2] = acc[2];
     if (l_z) *l_z = acc[3];
-    return NB_OK;
-}
-
-extern "C" int nb_collide_capacity(nb_sim *s, size_t max_pairs)
-{
-    if (!s) return nb_fail(NB_EINVAL, "nb_collide_capacity: NULL handle");
-    if (!s->collide) return nb_fail(NB_ESTATE, "nb_collide_capacity: the handle was created without NB_EXTRA_COLLIDE");
-    if (max_pairs == 0 || max_pairs > 0x7fffffffu) return nb_fail(NB_EINVAL, "nb_collide_capacity: max_pairs must be 1 .. 2^31 - 1");
-    if (s->in_step) return nb_fail(NB_ESTATE, "nb_collide_capacity: a split step is in flight");
-    if (bind(s)) return NB_EHIP;
-    HIPCHK(hipStreamSynchronize(s->stream));          // the pair rows of the steps enqueued so far
-    return collide_alloc_pairs(s, max_pairs);
-}
-
-extern "C" int nb_collision_stats(nb_sim *s, uint64_t *pairs_last_step, uint64_t *pairs_total, uint32_t *rounds_last_step,
-                                  uint64_t *overflow_steps)
-{
-    if (!s) return nb_fail(NB_EINVAL, "nb_collision_stats: NULL handle");
-    if (bind(s)) return NB_EHIP;
-    CollideStats c{};
-    int rc = NB_OK;
-    if (s->collide) {
-        rc = collide_check(s);
-        c = *s->coll_host;
-        if (rc && nb_last_error_code() != NB_ENOMEM) return rc;
-    }
-    if (pairs_last_step) *pairs_last_step = c.pairs_last;
-    if (pairs_total) *pairs_total = c.pairs_total;
-    if (rounds_last_step) *rounds_last_step = c.rounds_last;
-    if (overflow_steps) *overflow_steps = c.overflow_steps;
-    return rc;
-}
-
-extern "C" int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, uint64_t *overflow_steps)
-{
-    if (!s) return nb_fail(NB_EINVAL, "nb_tree_stats: NULL handle");
-    if (!s->tree) return nb_fail(NB_ESTATE, "nb_tree_stats: the handle was created with NB_FORCE_DIRECT");
-    if (bind(s)) return NB_EHIP;
-    const int rc = tree_check(s);
-    if (rc && nb_last_error_code() != NB_ENOMEM) return rc;
-    if (nodes) *nodes = s->tree_host->nodes;
-    if (max_depth) *max_depth = s->tree_host->max_depth;
-    if (overflow_steps) *overflow_steps = s->tree_host->overflow_steps;
-    return rc;
-}
-
-// Scratch of nb_tree_nodes for `total` nodes: 144 B per node on the device (record 128, flag 4, rank 8, index 4) plus the scan's
-// temporary storage, asked from nb_tree_scan for THIS element count (tree_tmp was sized for n + 2 elements).  Growth only, with an
-// eighth of slack so that a tree that grows a little every frame does not reallocate every frame; never above the node capacity.
-static int tree_export_alloc(nb_sim *s, uint64_t total)
-{
-    if (total <= s->tree_exp_cap) return NB_OK;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    for (void *q : {(void *)s->tree_exp_rec, (void *)s->tree_exp_flag, (void *)s->tree_exp_rank, (void *)s->tree_exp_idx, s->tree_exp_tmp})
-        (void)hipFree(q);
-    s->tree_exp_rec = nullptr; s->tree_exp_flag = nullptr; s->tree_exp_rank = nullptr; s->tree_exp_idx = nullptr; s->tree_exp_tmp = nullptr;
-    s->tree_exp_cap = 0;
-    const uint64_t cap = std::max<uint64_t>(total, std::min<uint64_t>(total + total / 8 + 1024, s->tree_cap));
-    HIPCHK(hipMalloc((void **)&s->tree_exp_rec, cap * sizeof(nb_tree_node)));
-    HIPCHK(hipMalloc((void **)&s->tree_exp_flag, cap * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_exp_rank, cap * sizeof(uint64_t)));
-    HIPCHK(hipMalloc((void **)&s->tree_exp_idx, cap * sizeof(uint32_t)));
-    size_t bytes = 0;
-    HIPCHK(nb_tree_scan(nullptr, bytes, s->tree_exp_flag, s->tree_exp_rank, (size_t)cap, s->stream));
-    s->tree_exp_tmp_bytes = std::max<size_t>(bytes, 256);
-    HIPCHK(hipMalloc(&s->tree_exp_tmp, s->tree_exp_tmp_bytes));
-    s->tree_exp_cap = cap;
-    return NB_OK;
-}
-
-// The reference's `quadtree.nodes` (main.cpp:626, drawQuadtreeNode main.cpp:394-475) for the tree of the last build.
-extern "C" int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size_t *count)
-{
-    if (!s || !count) return nb_fail(NB_EINVAL, "nb_tree_nodes: NULL %s", !s ? "handle" : "count");
-    if (!s->tree) return nb_fail(NB_ESTATE, "nb_tree_nodes: the handle was created with NB_FORCE_DIRECT");
-    if (s->in_step) return nb_fail(NB_ESTATE, "nb_tree_nodes: a split step is in flight");
-    if (bind(s)) return NB_EHIP;
-    { const int rc = step_check(s); if (rc) return rc; }          // synchronises; a pending failed-build report leaves through here, once
-    const TreeStats &t = *s->tree_host;
-    if (t.fail)
-        return nb_fail(NB_ESTATE, "nb_tree_nodes: no tree to export: the last build failed (%s)", t.fail == 1 ? "node capacity" : "depth cap");
-    const uint64_t total = t.nodes;                               // 0 before any build; <= tree_cap < 2^32 after a good one
-    if (total > s->tree_cap) return nb_fail(NB_ESTATE, "internal: nb_tree_nodes: %llu nodes in a capacity of %llu", (unsigned long long)total, (unsigned long long)s->tree_cap);
-    *count = (size_t)total;
-    if (!out || total == 0) return NB_OK;
-    if (capacity < total)
-        return nb_fail(NB_EINVAL, "nb_tree_nodes: the tree has %llu nodes, out holds %zu", (unsigned long long)total, capacity);
-    { const int rc = tree_export_alloc(s, total); if (rc) return rc; }
-    const size_t bytes = (size_t)total * sizeof(nb_tree_node);
-    const bool direct = pinned_covers(out, bytes);
-    if (!direct && s->tree_exp_stage_cap < total) {
-        if (s->tree_exp_stage) { (void)hipHostFree(s->tree_exp_stage); s->tree_exp_stage = nullptr; s->tree_exp_stage_cap = 0; }
-        HIPCHK(hipHostMalloc(&s->tree_exp_stage, (size_t)s->tree_exp_cap * sizeof(nb_tree_node), hipHostMallocDefault));
-        s->tree_exp_stage_cap = s->tree_exp_cap;
-    }
-    const uint32_t tot = (uint32_t)total;
-    const uint32_t g = (uint32_t)std::min<uint64_t>((total + 255u) / 256u, 8u * (uint32_t)s->cus);
-    std::pair<hipEvent_t, hipEvent_t> pr;                         // with nb_profile_enable the export kernels count as one launch
-    if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
-    tree_export_flags<<<g, 256, 0, s->stream>>>(s->tree_dp, tot, s->tree_exp_flag);
-    HIPCHK(hipGetLastError());
-    size_t tmp = s->tree_exp_tmp_bytes;
-    HIPCHK(nb_tree_scan(s->tree_exp_tmp, tmp, s->tree_exp_flag, s->tree_exp_rank, (size_t)total, s->stream));
-    tree_export_root<<<1, 64, 0, s->stream>>>(s->tree_nd, s->tree_dp, s->tree_root_dev, tot, s->tree_exp_rec, s->tree_exp_idx);
-    for (uint32_t level = 0; level < t.max_depth && level < (uint32_t)TREE_DEPTH_CAP; ++level)
-        tree_export_level<<<g, 256, 0, s->stream>>>(s->tree_nd, s->tree_nx, s->tree_dp, s->tree_exp_rank, level, tot, s->tree_exp_rec,
-                                                    s->tree_exp_idx);
-    HIPCHK(hipGetLastError());
-    if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
-    return copy_d2h(s, out, s->tree_exp_rec, bytes, s->stream, direct ? nullptr : s->tree_exp_stage);
-}
-
-// alpha travels to the walks as a kernel argument: the evaluations enqueued so far keep theirs, the next one takes the new value
-extern "C" int nb_tree_alpha(nb_sim *s, float alpha)
-{
-    if (!s) return nb_fail(NB_EINVAL, "nb_tree_alpha: NULL handle");
-    if (!s->tree_rel) return nb_fail(NB_ESTATE, "nb_tree_alpha: the handle was created without NB_FLAG_TREE_RELATIVE");
-    if (!(alpha >= 0.0f) || std::isinf(alpha)) return nb_fail(NB_EINVAL, "nb_tree_alpha: alpha must be finite and >= 0 (got %g)", (double)alpha);
-    if (s->in_step) return nb_fail(NB_ESTATE, "nb_tree_alpha: a split step is in flight");
-    s->tree_alpha = alpha;
     return NB_OK;
 }
 
@@ -2377,28 +1654,24 @@ extern "C" int nb_debug_fast_inv_sqrt(const float *x, float *y_scalar, float *y_
 {
     if (!x || !y_scalar || !y_packed || n == 0 || (n & 1) || n > 0x7fffff00u) return nb_fail(NB_EINVAL, "nb_debug_fast_inv_sqrt: bad arguments (n even)");
     if (nb_device_count() <= 0) return nb_fail(NB_ENODEVICE, "nb_debug_fast_inv_sqrt: no HIP device visible");
+    MemPool<HipMem> tmp;
     float *dx = nullptr, *ds = nullptr, *dp = nullptr, *host = nullptr;
-    int rc = NB_OK;
     hipError_t e;
     // page-locked staging: pageable caller memory is never handed to HIP (see copy_h2d)
-    if ((e = hipHostMalloc((void **)&host, 3 * n * sizeof(float), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipMalloc((void **)&dx, n * sizeof(float))) != hipSuccess || (e = hipMalloc((void **)&ds, n * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc((void **)&dp, n * sizeof(float))) != hipSuccess) {
-        rc = nb_fail(hip_code(e), "nb_debug_fast_inv_sqrt: allocation: %s", hipGetErrorString(e));
-    } else {
-        memcpy(host, x, n * sizeof(float));
-        if ((e = hipMemcpy(dx, host, n * sizeof(float), hipMemcpyHostToDevice)) == hipSuccess) {
-            quake_rsqrt_array<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK>>>(dx, ds, dp, (uint32_t)n);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpy(host + n, ds, n * sizeof(float), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(host + 2 * n, dp, n * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = nb_fail(hip_code(e), "nb_debug_fast_inv_sqrt: %s", hipGetErrorString(e));
-        else { memcpy(y_scalar, host + n, n * sizeof(float)); memcpy(y_packed, host + 2 * n, n * sizeof(float)); }
+    if ((e = tmp.alloc_pinned(host, 3 * n)) != hipSuccess || (e = tmp.alloc(dx, n)) != hipSuccess || (e = tmp.alloc(ds, n)) != hipSuccess ||
+        (e = tmp.alloc(dp, n)) != hipSuccess)
+        return nb_fail(hip_code(e), "nb_debug_fast_inv_sqrt: allocation: %s", hipGetErrorString(e));
+    memcpy(host, x, n * sizeof(float));
+    if ((e = hipMemcpy(dx, host, n * sizeof(float), hipMemcpyHostToDevice)) == hipSuccess) {
+        quake_rsqrt_array<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK>>>(dx, ds, dp, (uint32_t)n);
+        e = hipGetLastError();
     }
-    (void)hipFree(dx); (void)hipFree(ds); (void)hipFree(dp);
-    if (host) (void)hipHostFree(host);
-    return rc;
+    if (e == hipSuccess) e = hipMemcpy(host + n, ds, n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(host + 2 * n, dp, n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return nb_fail(hip_code(e), "nb_debug_fast_inv_sqrt: %s", hipGetErrorString(e));
+    memcpy(y_scalar, host + n, n * sizeof(float));
+    memcpy(y_packed, host + 2 * n, n * sizeof(float));
+    return NB_OK;
 }
 
 // Test hook: move the handle's item-ticket counters (device) and the host's record of them to `value`, as if the launches so far
@@ -2436,7 +1709,7 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
     const char *resolve = "none";
     if (s->collide) {
         if (bind(s) || collide_read(s)) return nb_last_error_code();     // the last step's record (an overflow stays unreported)
-        resolve = s->coll_host->touched == 0 ? "none" : s->coll_host->lds_last ? "lds" : "global";
+        resolve = s->coll.host->touched == 0 ? "none" : s->coll.host->lds_last ? "lds" : "global";
     }
     const int used = snprintf(buf, buflen,
              "n=%zu owned=[%zu,+%zu) %s%s rsqrt=%s sum=%s | force: block=%d waves/i-set=%d i/lane=%d i_tiles=%u j_slices(all)=%u grid=%u tile_j=%d | "
@@ -2449,17 +1722,17 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
              (int)symmetric(s), s->sym_sb, (int)sym_uses_pairs(s), s->sym_items, s->sym_L, s->sym_items_late,
              (double)s->sym_info.slab_s_bytes / 1048576.0, (double)s->sym_info.slab_r_bytes / 1048576.0, s->cus);
     if (used >= 0 && (size_t)used < buflen)
-        snprintf(buf + used, buflen - (size_t)used, " | collide=%d h=%.6g large=%u capacity=%llu resolve=%s", (int)s->collide, s->coll_h,
-                 s->coll_large_n, (unsigned long long)s->coll_cap, resolve);
+        snprintf(buf + used, buflen - (size_t)used, " | collide=%d h=%.6g large=%u capacity=%llu resolve=%s", (int)s->collide, s->coll.h,
+                 s->coll.large_n, (unsigned long long)s->coll.cap, resolve);
     const size_t len = strlen(buf);
     if (len < buflen) {
         if (s->tree) snprintf(buf + len, buflen - len, " | force=tree theta=%.6g node_capacity=%llu depth_cap=%d%s%s%s", (double)s->p.theta,
-                              (unsigned long long)s->tree_cap, TREE_DEPTH_CAP,
-                              !s->tree_leaves ? "" : tree_walk_is_group(s) ? " leaves=1 walk=group" : " leaves=1 walk=lane",
-                              s->tree_quad ? " quad=1" : "", s->tree_energy ? " energy=tree" : "");
+                              (unsigned long long)s->bh.cap, TREE_DEPTH_CAP,
+                              !s->bh.leaves ? "" : tree_walk_is_group(s) ? " leaves=1 walk=group" : " leaves=1 walk=lane",
+                              s->bh.quad ? " quad=1" : "", s->bh.energy ? " energy=tree" : "");
         else snprintf(buf + len, buflen - len, " | force=direct");
         const size_t len2 = strlen(buf);
-        if (s->tree_rel && len2 < buflen) snprintf(buf + len2, buflen - len2, " alpha=%.6g", (double)s->tree_alpha);
+        if (s->bh.rel && len2 < buflen) snprintf(buf + len2, buflen - len2, " alpha=%.6g", (double)s->bh.alpha);
     }
     return NB_OK;
 }

@@ -9,6 +9,8 @@
 //    lists consistent with the segments.
 // 2. host I/O: write/read round trips, truncated and forged headers (a forged body count must be refused
 //    before any buffer is sized from it), the generators at ragged sizes.
+// 3. memory pool (nb_mem.h) over malloc / free: random allocate / release / regrow / release_all sequences with a backend
+//    that refuses its k-th request; allocations and frees balance, no pointer outlives its block.
 #include <unistd.h>
 
 #include <algorithm>
@@ -19,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "nb_mem.h"
 #include "nb_plan.h"
 #include "nb_sched.h"
 #include "nbody.h"
@@ -259,6 +262,87 @@ static void fuzz_idfile(const std::string &dir, std::mt19937 &rng)
     REQUIRE(nb_comm_id_publish(nullptr, 1, id) == NB_EINVAL && nb_comm_id_await(path.c_str(), 1, nullptr, 10) == NB_EINVAL, "NULL arguments");
 }
 
+// The pool of nb_mem.h over malloc / free.  The backend counts its calls and refuses request number `fail_at` (0: none).
+struct MallocMem {
+    using error = int;
+    static constexpr error ok = 0, misuse = -2;
+    static inline long allocs = 0, frees = 0, requests = 0, fail_at = 0, pinned_live = 0;
+    static error get(void **p, size_t bytes)
+    {
+        if (++requests == fail_at) return -1;
+        *p = std::malloc(bytes ? bytes : 1);
+        REQUIRE(*p, "malloc(%zu)", bytes);
+        std::memset(*p, 0xA5, bytes);             // the whole block is the caller's to write
+        ++allocs;
+        return ok;
+    }
+    static error device(void **p, size_t bytes) { return get(p, bytes); }
+    static error pinned(void **p, size_t bytes) { const error e = get(p, bytes); if (e == ok) ++pinned_live; return e; }
+    static void free_device(void *p) { REQUIRE(p, "free of a null block"); std::free(p); ++frees; }
+    static void free_pinned(void *p) { free_device(p); --pinned_live; }       // a block goes back the way it came
+};
+
+static int fuzz_pool(int cases, std::mt19937 &rng)
+{
+    for (int c = 0; c < cases; ++c) {
+        MallocMem::allocs = MallocMem::frees = MallocMem::requests = MallocMem::pinned_live = 0;
+        MallocMem::fail_at = rng() % 3 ? 1 + (long)(rng() % 40) : 0;
+        uint32_t *slot[12] = {};                                        // the handle's fields: fixed addresses
+        void *raw[4] = {};                                              // byte-sized blocks (void *)
+        size_t live = 0;
+        {
+            MemPool<MallocMem> pool;
+            auto attempt = [&](auto &p, size_t count, bool pinned) -> bool { // one allocation and what must hold after it; true: a new block
+                const size_t before = pool.size();
+                const bool was_null = p == nullptr;
+                const auto old = p;
+                const long asked = MallocMem::requests;
+                const int e = pinned ? pool.alloc_pinned(p, count) : pool.alloc(p, count);
+                if (!was_null) { REQUIRE(e == MallocMem::misuse && p == old && pool.size() == before && MallocMem::requests == asked, "overwrite"); return false; }
+                if (e != MallocMem::ok) { REQUIRE(e == -1 && p == nullptr && pool.size() == before, "a failed allocation left something behind"); return false; }
+                REQUIRE(p != nullptr && pool.size() == before + 1, "allocation not recorded");
+                ++live;
+                return true;
+            };
+            const int ops = 1 + (int)(rng() % 60);
+            for (int k = 0; k < ops; ++k) {
+                const unsigned what = rng() % 10, i = rng() % 12, j = rng() % 4;
+                const size_t count = rng() % 5 ? 1 + rng() % 3000 : 0;
+                if (what < 4) {
+                    if (attempt(slot[i], count, rng() % 4 == 0) && count) slot[i][count - 1] = 7;           // typed: count elements, not bytes
+                } else if (what < 5) {
+                    if (attempt(raw[j], count, rng() % 2 == 0) && count) ((char *)raw[j])[count - 1] = 7;
+                } else if (what < 7) {                                       // release (a null pointer: nothing happens)
+                    const size_t before = pool.size();
+                    const bool had = slot[i] != nullptr;
+                    pool.release(slot[i]);
+                    REQUIRE(slot[i] == nullptr && pool.size() == before - (had ? 1 : 0), "release");
+                    live -= had ? 1 : 0;
+                } else if (what < 9) {                                       // the regrow sites: release, then allocate larger
+                    live -= slot[i] ? 1 : 0;
+                    pool.release(slot[i]);
+                    attempt(slot[i], count + 1 + rng() % 5000, false);
+                } else if (rng() % 4 == 0) {
+                    pool.release_all();
+                    live = 0;
+                    for (auto *q : slot) REQUIRE(q == nullptr, "release_all left a pointer");
+                    for (auto *q : raw) REQUIRE(q == nullptr, "release_all left a pointer");
+                    REQUIRE(MallocMem::allocs == MallocMem::frees, "release_all left a block");
+                }
+                REQUIRE(pool.size() == live && (size_t)(MallocMem::allocs - MallocMem::frees) == live, "the pool's record and the backend disagree");
+            }
+            uint32_t *foreign = (uint32_t *)&live;                          // not the pool's: left alone
+            pool.release(foreign);
+            REQUIRE(foreign == (uint32_t *)&live && pool.size() == live, "release of a foreign pointer");
+            if (rng() % 2) pool.release_all();                              // ... or the destructor
+        }
+        REQUIRE(MallocMem::allocs == MallocMem::frees && MallocMem::pinned_live == 0, "case %d: %ld allocations, %ld frees", c, MallocMem::allocs, MallocMem::frees);
+        for (auto *q : slot) REQUIRE(q == nullptr, "a pointer outlived the pool");
+        for (auto *q : raw) REQUIRE(q == nullptr, "a pointer outlived the pool");
+    }
+    return cases;
+}
+
 int main(int argc, char **argv)
 {
     const int cases = argc > 1 ? std::atoi(argv[1]) : 300;
@@ -269,6 +353,7 @@ int main(int argc, char **argv)
     fuzz_host(dir, rng);
     fuzz_schedule(cases, rng);
     fuzz_idfile(dir, rng);
-    std::printf("OK planner_cases=%d seed=%u\n", cases, seed);
+    const int pool_cases = fuzz_pool(cases, rng);
+    std::printf("OK planner_cases=%d seed=%u pool_cases=%d\n", cases, seed, pool_cases);
     return 0;
 }

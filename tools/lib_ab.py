@@ -7,9 +7,10 @@ final bodies compared bit for bit (sha256 of pos | vel | acc) and timed.  For ch
 
 A case is [MODS-]BASE<n>.  BASE: p 2-D fp32, d 2-D fp64, q 3-D fp32, qd 3-D fp64, ref the reference start.  MODS, letters
 in any order: o one-sided (symmetry=False), g eps = 0 (the guarded body, one-sided), k rsqrt="quake", s mass scaling in the
-individual-masses run (uniform_mass=False, mass_scaling=True); the Barnes-Hut force: t force="tree" at theta = 0.5, l tree_leaves=True,
+individual-masses run (uniform_mass=False, mass_scaling=True), c collisions (extras |= NB_EXTRA_COLLIDE, on the ref base: its bodies
+have radii); the Barnes-Hut force: t force="tree" at theta = 0.5, l tree_leaves=True,
 u tree_quadrupole=True, r tree_alpha=0.02, e tree_energy=True (the hash then also covers the two doubles of energy() read after the
-steps).  Example: og-qd4096, os-p65536, tlur-p4096.  A combination Simulation rejects ends the run with its message.
+steps).  Example: og-qd4096, os-p65536, c-ref25000, tlur-p4096.  A combination Simulation rejects ends the run with its message.
 
 (the Python binding loads $NBODY_HIP_LIB when set — the LIBRARY reads no environment variables; each side runs in a child process)
 """
@@ -50,6 +51,8 @@ def child(cases, steps):
             kw["eps"] = 0.0
         if "k" in mods:
             kw["rsqrt"] = "quake"
+        if "c" in mods:
+            kw["extras"] = kw.get("extras", 0) | 4   # NB_EXTRA_COLLIDE
         if "t" in mods:
             kw.update(force="tree", theta=0.5)
         if "l" in mods:
