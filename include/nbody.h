@@ -507,6 +507,50 @@ int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, uint64_t *ove
  * it.  With nb_profile_enable the export kernels are bracketed like a force launch and count as one (nb_profile_read). */
 int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size_t *count);
 
+/* The frame whose size is the screen's: how many bodies, and how much mass, fall into each pixel of a view, binned on the device and
+ * copied out as width x height values whatever n is.  Replaces, for systems too large to copy and draw body by body, the reference's
+ * render loop (main.cpp:745-835: one quad per visible body after worldToScreen / isInScreenBounds, :196-213) and the copy of the
+ * bodies that feeds it: the caller uploads one texture.
+ * WHICH BODIES: the owned block of the handle, at the positions of all work enqueued so far, exactly as nb_sync_positions defines
+ * them; an NB_FP64 handle's positions and masses are rounded to float first; a dims = 3 handle is projected on (x, y).  Every kind of
+ * handle: direct or tree, any flags, sharded or not (the count planes of the ranks of a sharded run add up to the unsharded one).
+ * PIXEL OF A BODY: fp32, one rounding per operation, no contraction, the reference's worldToScreen:
+ *     sx = (x - center_x) * scale + width * 0.5f        sy = (y - center_y) * scale + height * 0.5f
+ * The body is inside when sx >= 0 && sx < (float)width && sy >= 0 && sy < (float)height, tested BEFORE any conversion (sx = -0.5 is
+ * outside; a NaN or infinite coordinate is outside); its pixel is then p = (uint32_t)sy * width + (uint32_t)sx: rows in y order,
+ * row-major.  The reference's 1000-pixel culling margin is not reproduced: the image is the screen.
+ * OUTPUTS: count[p] = bodies in pixel p, massless ones included.  mass[p] is built in exact integer units: a body contributes u = 0
+ * when !(m > 0) (zero, negative, NaN), otherwise r = m / mass_quantum (fp32) and u = r >= 4294967296.0f ? 4294967295 :
+ * (uint32_t)rintf(r) (ties to even); the units of a pixel are summed as 64-bit integers U_p (n <= 2^31 bodies of at most 2^32 - 1
+ * units cannot overflow) and mass[p] = (float)((double)U_p * (double)mass_quantum).  No floating-point atomics anywhere.  CONSEQUENCES:
+ * two handles agree bit for bit, and permuting the bodies leaves both planes unchanged bit for bit.
+ * Either of count / mass may be NULL, not both; a plane that is not asked for costs no pass and no copy, and is not written.  The
+ * destinations (width * height elements each) may be any host memory, as for nb_sync: ranges known to be page-locked (nb_host_alloc /
+ * nb_host_register) are written by the copy engine directly, anything else moves through page-locked staging of the library's.
+ * ERRORS: NB_EINVAL, naming the field, before any device work: NULL handle, view or both planes; struct_size != sizeof(nb_view);
+ * width or height 0 or above 16384, or width * height > 2^24; scale not finite or <= 0; a non-finite centre; _reserved0 != 0;
+ * mass != NULL with mass_quantum not finite or <= 0.  NB_ESTATE while a split step is in flight.  The call synchronises; a pending
+ * once-only report (collision capacity, failed tree build) leaves through it as through nb_sync_positions (NB_ENOMEM, once), and
+ * nothing is written to the planes then.
+ * Nothing of the handle changes: positions, velocities, acc[], frame counter, tree arrays and nb_tree_stats are untouched, and the
+ * next step is bit-identical to one on a handle that never called this.
+ * Memory: nothing until the first call; then, per pixel of the largest view seen (growth only, freed by nb_destroy): 4 bytes on the
+ * device for the counts; 8 + 4 bytes more (unit sums, float plane) once a mass plane is asked for; 4 bytes of page-locked host staging
+ * once a destination needs it: 4 / 12 / 4 MiB for a 1024 x 1024 view.  Cost: adds that share a pixel are combined inside the wave and
+ * inside the workgroup (LDS) before they reach memory, so the worst case for atomics, every body in ONE pixel, is not the slow one:
+ * on an MI355X the bin pass of a 1024 x 1024 view at scale 1e-3 (all bodies in the four pixels round the centre) takes 0.052 ms at
+ * 1 048 576 bodies and 0.066 ms (counts) / 0.123 ms (both planes) at 8 388 608, where one global add per body takes 3.1 ms at
+ * 1 048 576; the whole call, both planes into pageable memory, 0.45 and 0.51 ms (profiles/raster_bench.log).
+ * With nb_profile_enable the bin pass is bracketed like a force launch and counts as one (nb_profile_read). */
+typedef struct nb_view {
+    uint32_t struct_size;      /* = sizeof(nb_view), set by the caller */
+    uint32_t width, height;    /* pixels: 1 .. 16384 each, width * height <= 2^24 */
+    float    center_x, center_y, scale;   /* the reference's worldToScreen, main.cpp:196-201 */
+    float    mass_quantum;     /* > 0 and finite when a mass plane is asked for; ignored otherwise */
+    uint32_t _reserved0;       /* must be 0 */
+} nb_view;
+int nb_raster(nb_sim *s, const nb_view *view, uint32_t *count, float *mass);
+
 /* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
  * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without
  * the flag.  At creation alpha is 0.005: GADGET-2's customary ErrTolForceAcc, not a number measured for this library.  A setter

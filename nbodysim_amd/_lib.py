@@ -151,6 +151,21 @@ class nb_sym_info(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "struct_size" and not k.startswith("_")}
 
 
+class nb_view(C.Structure):
+    """A view for ``nb_raster`` (include/nbody.h): the reference's worldToScreen parameters and the image size."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("center_x", C.c_float),
+        ("center_y", C.c_float),
+        ("scale", C.c_float),
+        ("mass_quantum", C.c_float),
+        ("_reserved0", C.c_uint32),
+    ]
+
+
 #: numpy view of ``nb_sym_item`` (32 bytes)
 SYM_ITEM_DTYPE = np.dtype([("tile", "<u4"), ("c0", "<u4"), ("cnt", "<u4"), ("s_row", "<u4"), ("r_base", "<i8"),
                            ("diag", "<u4"), ("group", "<u4")])
@@ -192,6 +207,7 @@ PROTOTYPES = {
     "nb_tree_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "nb_tree_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nb_tree_alpha": (C.c_int, [C.c_void_p, C.c_float]),
+    "nb_raster": (C.c_int, [C.c_void_p, C.POINTER(nb_view), C.c_void_p, C.c_void_p]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),
     "nb_owned_begin": (C.c_size_t, [C.c_void_p]),

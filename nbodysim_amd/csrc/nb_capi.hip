@@ -536,9 +536,10 @@ static int fence_foreign_work(nb_sim *s)
     return NB_OK;
 }
 
-// ---- the two subsystems' host code (it moves its data with copy_h2d / copy_d2h above) ----
+// ---- the subsystems' host code (it moves its data with copy_h2d / copy_d2h above) ----
 #include "nb_collide_host.hip.h"
 #include "nb_tree_host.hip.h"
+#include "nb_raster_host.hip.h"
 
 // what every synchronising call reports once: a collision step over capacity, a failed tree build
 static int step_check(nb_sim *s)

@@ -1,6 +1,6 @@
 // nb_sim.hip.h — the handle behind the C ABI, and what every piece of host code around it needs: the HIP error check, the
 // device binding, the dispatchers from run-time choices to template arguments.  Included by nb_capi.hip (the one device
-// translation unit) ahead of the host sides of the two subsystems, nb_collide_host.hip.h and nb_tree_host.hip.h.
+// translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h and nb_raster_host.hip.h.
 #pragma once
 #include "nbody.h"
 #include "nbody_debug.h"
@@ -9,6 +9,7 @@
 #include "nb_kernels3d.hip.h"
 #include "nb_collide.hip.h"
 #include "nb_tree.hip.h"
+#include "nb_raster.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -212,6 +213,17 @@ struct nb_sim {
             uint64_t stage_cap = 0;            // nodes it holds
         } exp;
     } bh;
+
+    // nb_raster (nb_raster.hip.h): nothing in `ras` exists before the first call; grown by the largest view seen
+    struct Raster {
+        uint64_t cap = 0;                      // pixels `cnt` holds
+        uint32_t *cnt = nullptr;               // the count plane
+        uint64_t mass_cap = 0;                 // pixels `units` and `massf` hold: nothing before the first mass plane
+        unsigned long long *units = nullptr;   // mass in quanta, summed as integers
+        float *massf = nullptr;                // the mass plane
+        void *stage = nullptr;                 // page-locked host staging for destinations the library does not know to be page-locked
+        uint64_t stage_cap = 0;                // pixels (4 B each) it holds
+    } ras;
 
     // profiling
     bool prof = false;

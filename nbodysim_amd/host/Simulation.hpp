@@ -223,6 +223,10 @@ public:
     }
     // After editing `bodies` in place on the host (same count).
     void upload() { check_size(); check(nb_upload(sim_, reinterpret_cast<const nb_body *>(bodies.data())), "nb_upload"); }
+    // The frame as an image instead of as bodies (nb_raster, include/nbody.h): bodies, and mass in quanta, per pixel of `view`, binned
+    // on the device at the positions of the work enqueued so far; `bodies` is not refreshed and need not be.  Replaces the per-body draw
+    // loop of main.cpp:745-835 by one texture upload.  Either plane may be null, not both; each holds view.width * view.height elements.
+    void raster(const nb_view &view, uint32_t *count, float *mass) { check(nb_raster(sim_, &view, count, mass), "nb_raster"); }
     nb_sim *handle() { return sim_; }
 
 private:

@@ -18,6 +18,9 @@
  *                            they otherwise sweep all n^2 / 2 pairs in fp64
  *              [-alpha A]    with -tree -leaves: the acceleration-relative opening test (NB_FLAG_TREE_RELATIVE, nb_tree_alpha): a cell
  *                            is accepted only if m size^2 / d^4 < A |a_prev| as well; theta stays the cap
+ *              [-raster W H FILE]  after the run: the count plane (nb_raster) of the W x H view that frames all bodies, written to FILE
+ *                            as a binary 16-bit PGM (P5, maxval 65535, big-endian, counts saturated): the way to look at a run too
+ *                            large to dump and draw body by body.  Single handle only (not with -shards / -rank)
  *              [-collide]    end every step with the reference's hard-sphere collisions (NB_EXTRA_COLLIDE, Simulation.hpp:216-346)
  *              [-shards P]   P sharded handles driven from this one process (device r mod #GPUs),
  *                            exchanged with nb_exchange_positions: multi-GPU without RCCL
@@ -73,6 +76,54 @@ static void on_deadline(int sig)
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); exit(1); } while (0)
 #define CHECK(call) do { int rc_ = (call); if (rc_ != NB_OK) DIE("%s -> %d: %s", #call, rc_, nb_last_error()); } while (0)
 
+/* -raster: the view that frames the finite positions of bodies[0..n) (a hair inside, so that the largest x and y stay below the
+ * exclusive right / bottom edge), its count plane from the device, saturated into a 16-bit PGM */
+static void write_raster(nb_sim *sim, const nb_body *bodies, size_t n, unsigned w, unsigned h, const char *path)
+{
+    float lo[2] = {0.f, 0.f}, hi[2] = {0.f, 0.f};
+    int any = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const float x = bodies[i].pos.x, y = bodies[i].pos.y;
+        if (!(x - x == 0.0f) || !(y - y == 0.0f)) continue;          /* NaN or infinite: outside every view */
+        if (!any) { lo[0] = hi[0] = x; lo[1] = hi[1] = y; any = 1; }
+        if (x < lo[0]) lo[0] = x;
+        if (x > hi[0]) hi[0] = x;
+        if (y < lo[1]) lo[1] = y;
+        if (y > hi[1]) hi[1] = y;
+    }
+    nb_view v;
+    memset(&v, 0, sizeof v);
+    v.struct_size = (uint32_t)sizeof v;
+    v.width = w; v.height = h;
+    v.center_x = 0.5f * lo[0] + 0.5f * hi[0];
+    v.center_y = 0.5f * lo[1] + 0.5f * hi[1];
+    const float dx = hi[0] - lo[0], dy = hi[1] - lo[1];
+    const float sx = dx > 0.0f ? (float)w / dx : 3.0e38f, sy = dy > 0.0f ? (float)h / dy : 3.0e38f;
+    v.scale = sx < sy ? sx : sy;
+    v.scale = v.scale < 3.0e38f ? 0.998f * v.scale : 1.0f;
+    const size_t px = (size_t)w * h;
+    uint32_t *count = (uint32_t *)malloc(px * sizeof *count);
+    unsigned char *img = (unsigned char *)malloc(px * 2);
+    if (!count || !img) DIE("-raster: out of memory for %u x %u pixels", w, h);
+    CHECK(nb_raster(sim, &v, count, NULL));
+    unsigned long long inside = 0;
+    uint32_t peak = 0;
+    for (size_t k = 0; k < px; ++k) {
+        const uint32_t c = count[k], g = c > 65535u ? 65535u : c;
+        inside += c;
+        if (c > peak) peak = c;
+        img[2 * k] = (unsigned char)(g >> 8);
+        img[2 * k + 1] = (unsigned char)(g & 255u);
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) DIE("-raster: cannot open %s", path);
+    if (fprintf(f, "P5\n%u %u\n65535\n", w, h) < 0 || fwrite(img, 2, px, f) != px || fclose(f) != 0) DIE("-raster: cannot write %s", path);
+    printf("raster %u x %u: centre (%g, %g) scale %g, %llu of %zu bodies inside, fullest pixel %u -> %s\n", w, h, v.center_x, v.center_y, v.scale,
+           inside, n, peak, path);
+    free(img);
+    free(count);
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 65536;
@@ -83,7 +134,8 @@ int main(int argc, char **argv)
     unsigned long long nonce = 0;
     const char *idfile = NULL;
     unsigned seed = 42;
-    const char *dump = NULL, *load = NULL;
+    const char *dump = NULL, *load = NULL, *raster = NULL;
+    unsigned raster_w = 0, raster_h = 0;
     nb_params p;
     nb_params_default(&p);
     p.eps = 0.01f;
@@ -112,6 +164,9 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-tree-energy")) p.flags |= NB_FLAG_TREE_ENERGY;
         else if (!strcmp(argv[i], "-alpha") && i + 1 < argc) { p.flags |= NB_FLAG_TREE_RELATIVE; alpha = (float)atof(argv[++i]); alpha_given = 1; }
         else if (!strcmp(argv[i], "-dump") && i + 1 < argc) dump = argv[++i];
+        else if (!strcmp(argv[i], "-raster") && i + 3 < argc) {
+            raster_w = (unsigned)strtoul(argv[++i], NULL, 10); raster_h = (unsigned)strtoul(argv[++i], NULL, 10); raster = argv[++i];
+        }
         else if (!strcmp(argv[i], "-load") && i + 1 < argc) {
             /* the header's parameters become the defaults of this run; later options override them */
             load = argv[++i];
@@ -139,6 +194,7 @@ int main(int argc, char **argv)
         else DIE("unknown argument %s", argv[i]);
     }
 
+    if (raster && (world > 0 || shards > 1 || (shards_given && rccl))) DIE("-raster: single handle only (not with -shards / -rank)");
     nb_body *bodies;
     if (reference_ics && !n_given) n = 25000;
     /* page-locked host memory from the library: nb_sync DMAs straight into it (a malloc'ed array works too, staged) */
@@ -311,6 +367,7 @@ int main(int argc, char **argv)
         CHECK(nb_dump(sim, dump));
         printf("dumped to %s\n", dump);
     }
+    if (raster) write_raster(sim, bodies, n, raster_w, raster_h, raster);
     nb_destroy(sim);
     CHECK(nb_host_free(bodies));
     return 0;

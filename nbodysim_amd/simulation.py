@@ -265,6 +265,49 @@ class Simulation:
             L.check("nb_tree_nodes", self._lib.nb_tree_nodes(self._h, out.ctypes.data, out.shape[0], C.byref(cnt)), self._lib)
         return out[: cnt.value]
 
+    def raster(self, width: int, height: int, center=(0.0, 0.0), scale: float = 1.0, mass_quantum: Optional[float] = None, out=None):
+        """The owned bodies binned into a ``(height, width)`` image on the device (``nb_raster``; synchronises): the reference's
+        worldToScreen with ``center`` and ``scale``, pixel ``[int(sy), int(sx)]``.  Returns the uint32 count plane; with a
+        ``mass_quantum`` returns ``(count, mass)``, mass a float32 plane summed in whole quanta (include/nbody.h).  ``out``: a
+        C-contiguous ``(height, width)`` uint32 array for the counts, or a pair ``(count, mass)`` of which either may be None: a
+        plane given as None in the pair is not computed and None is returned in its place (``mass`` needs a ``mass_quantum``).
+        Arrays over ``nb_host_alloc`` memory are written by the copy engine directly."""
+        # refused here, by name, before anything is allocated (the c_uint32 fields of nb_view would wrap a negative silently)
+        for name, val in (("width", width), ("height", height)):
+            if not 1 <= val <= 16384:
+                raise ValueError(f"raster: {name} must be 1 .. 16384 (got {val})")
+        if width * height > 1 << 24:
+            raise ValueError(f"raster: width * height must be <= 2^24 (got {width} x {height})")
+        count = mass = None
+        want_count, want_mass = True, mass_quantum is not None
+        if isinstance(out, (tuple, list)):
+            count, mass = out
+            want_count = count is not None
+            want_mass = mass is not None
+            if want_mass and mass_quantum is None:
+                raise ValueError("a mass plane needs a mass_quantum")
+        elif out is not None:
+            count = out
+        for name, a, dt in (("count", count, np.uint32), ("mass", mass, np.float32)):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != (height, width) or not a.flags.c_contiguous
+                                  or not a.flags.writeable):
+                raise TypeError(f"out: the {name} plane must be a writeable C-contiguous ({height}, {width}) numpy array of {np.dtype(dt).name}")
+        if want_count and count is None:
+            count = np.empty((height, width), dtype=np.uint32)
+        if want_mass and mass is None:
+            mass = np.empty((height, width), dtype=np.float32)
+        v = L.nb_view()
+        v.struct_size = C.sizeof(L.nb_view)
+        v.width, v.height = width, height
+        v.center_x, v.center_y = center
+        v.scale = scale
+        v.mass_quantum = 0.0 if mass_quantum is None else mass_quantum
+        L.check("nb_raster", self._lib.nb_raster(self._h, C.byref(v), count.ctypes.data if want_count and count is not None else None,
+                                                 mass.ctypes.data if want_mass and mass is not None else None), self._lib)
+        if isinstance(out, (tuple, list)) or mass_quantum is not None:
+            return (count if want_count else None), (mass if want_mass else None)
+        return count
+
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
         L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)

@@ -13,6 +13,10 @@ u tree_quadrupole=True, r tree_alpha=0.02, e tree_energy=True (the hash then als
 steps).  Example: og-qd4096, os-p65536, c-ref25000, tlur-p4096.  A combination Simulation rejects ends the run with its message.
 
 (the Python binding loads $NBODY_HIP_LIB when set — the LIBRARY reads no environment variables; each side runs in a child process)
+
+When the current binding declares an entry point the old library does not have yet (it refuses to bind a library that lacks a
+declared symbol), give the old side its own binding too: --old-pkg DIR, a directory holding the old commit's `nbodysim_amd` package
+with its library inside (cp -r /tmp/old/nbodysim_amd build/old_pkg/); --old is then not used.
 """
 import argparse
 import hashlib
@@ -30,7 +34,9 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 
-def child(cases, steps):
+def child(cases, steps, pkg=None):
+    if pkg:
+        sys.path.insert(0, str(Path(pkg).resolve()))
     import nbodysim_amd as nb
     out = {}
     for name in cases:
@@ -94,19 +100,24 @@ def main():
     ap.add_argument("--old", default=str(ROOT / "build" / "old_lib" / "libnbody_hip.so"))
     ap.add_argument("--cases", default="p9216,p16384,ref25000,p32768,p65536,p131072")
     ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--old-pkg", default=None)
+    ap.add_argument("--pkg", default=None)
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     cases = args.cases.split(",")
     if args.child:
-        child(cases, args.steps)
+        child(cases, args.steps, args.pkg)
         return
     res = {}
     for tag, lib in (("old", args.old), ("new", None), ("old2", args.old), ("new2", None)):
         env = dict(os.environ)
         env.pop("NBODY_HIP_LIB", None)
-        if lib:
+        extra = []
+        if lib and args.old_pkg:
+            extra = ["--pkg", args.old_pkg]
+        elif lib:
             env["NBODY_HIP_LIB"] = str(Path(lib).resolve())
-        r = subprocess.run([sys.executable, __file__, "--child", "--cases", args.cases, "--steps", str(args.steps)], env=env, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, __file__, "--child", "--cases", args.cases, "--steps", str(args.steps), *extra], env=env, capture_output=True, text=True, timeout=600)
         if r.returncode:
             print(tag, r.stderr[-2000:])
             sys.exit(1)
