@@ -465,6 +465,47 @@ int nb_energy(nb_sim *s, double *kinetic, double *potential);
  * rounding, whatever the softening; a sharded handle returns its owned block's share (the shares add up). */
 int nb_momentum(nb_sim *s, double *p_xyz, double *l_z);
 
+/* The potential of every owned body, the per-body counterpart of nb_energy:
+ *     phi[i] = - sum_{j != i} m_j / sqrt(|x_j - x_i|^2 + eps^2)        (G = 1, the softening of the force)
+ * so that the binding energy of body i is v_i^2 / 2 + phi[i], the bound members are those below 0 and the most-bound body is a
+ * centre; 1/2 sum m_i phi[i] over all bodies is the *potential of nb_energy.
+ * WHICH BODIES: phi[0 .. nb_owned_count(s)), the owned block of the handle at the positions of all work enqueued so far, exactly as
+ * nb_sync_positions defines them; the j-sum runs over all n bodies of the CURRENT replica (on a sharded handle it must be
+ * complete, as for nb_energy).  Every kind of handle: fp32 and fp64, dims 2 and 3, either integrator, sharded or not, direct or
+ * tree with any flags.  A massless body gets a phi too: the field potential at a tracer.
+ * THE SELF TERM is left out by index (j != i), not by distance: bodies that share i's position each add -m_j / eps, nb_energy's
+ * pair convention.  With eps = 0 a body that shares its position with another gets a value that is NOT FINITE (nb_energy's
+ * infinity); every other body's value is finite.
+ * ARITHMETIC of the direct sweep (every handle but a NB_FLAG_TREE_ENERGY one; a tree handle without that flag, the reference-
+ * arithmetic one without leaves included, runs it too: "exact O(n^2) unless the handle has the flag", as nb_energy).  NB_FP64: fp64
+ * throughout, the terms added in j order (1.4e-16 per reciprocal square root): within n x 1.1e-16 of the exact sum.  NB_FP32
+ * (whatever rsqrt_mode and sum_order): fp32 terms m_j x v_rsq_f32(r^2) summed in fp32 over runs of 64 consecutive j, the runs added in
+ * fp64, the result fp64: within 4e-6 relative of the fp64 sum of the same float positions (3.5 ulp per term and the 63 roundings of
+ * a same-signed run; tests/potential_model.py is the numpy statement).
+ * DETERMINISM: two handles agree bit for bit.  On the direct sweep phi[i] depends on the bodies, eps, the precision and i only, not
+ * on the owned block or the launch geometry (the j-tiles always start at j = 0 and the partial sums are added in one fixed order): a
+ * handle that owns [i_begin, i_begin + i_count) returns the bits of that slice of the unsharded handle's result.
+ * NB_FLAG_TREE_ENERGY handles: the tree build and the potential walk of nb_energy run, and phi[i] is the walker's value (the bodies on
+ * its own position included), written instead of reduced: the cells, the windows of 64, the "walks alone" rule, the quadrupole and
+ * relative tests, the fp64 terms and the leaf residual are nb_energy's (tests/tree_energy_model.py, phi).  eps = 0 skips the pairs
+ * on one position (finite), as nb_energy does there.  Massless bodies walk alone, as in the force walk (in nb_energy they do not
+ * walk); one that lies exactly on an inserted position takes no term from that leaf (d^2 = 0): the one difference from the direct
+ * sweep.  Permuting the bodies leaves the visited terms unchanged; phi changes through the order of the sum only.  As for nb_energy
+ * the tree arrays are rebuilt, nb_tree_stats describes this build, and a failed build makes THIS call return NB_ENOMEM through the
+ * once-only report, phi not written.
+ * Nothing else of the handle changes: positions, velocities, acc[] and the frame counter are untouched, and the next step is
+ * bit-identical to one on a handle that never called this.
+ * ERRORS: NB_EINVAL for a NULL handle or a NULL phi, before any device work; NB_ESTATE while a split step is in flight.  The call
+ * synchronises; a pending once-only report (collision capacity, failed tree build) leaves through it as through nb_sync_positions
+ * (NB_ENOMEM, once), and nothing is written to phi then.  phi may be any host memory, as for nb_sync: ranges known to be page-locked
+ * (nb_host_alloc / nb_host_register) are written by the copy engine directly, anything else moves through the staging buffer of
+ * nb_sync.  Memory: 8 bytes per owned body on the device from the first call on (freed by nb_destroy).  With nb_profile_enable the
+ * sweep (the two walk kernels on a NB_FLAG_TREE_ENERGY handle) is bracketed like a force launch and counts as one (nb_profile_read).
+ * Cost on an MI355X, fp32 2-D, into a pageable array (profiles/potential_bench.log): the direct sweep 10.4 ms at 262 144 bodies and
+ * 145 ms at 1 048 576 (a one-sided force evaluation of the same handles: 12.1 and 195 ms); a NB_FLAG_TREE_ENERGY handle at
+ * theta = 0.5: 2.9 ms at 1 048 576 and 20 ms at 8 388 608. */
+int nb_potentials(nb_sim *s, double *phi);
+
 /* Collisions (NB_EXTRA_COLLIDE).  nb_collide_capacity sets the pair capacity (1 .. 2^31 - 1) between steps; NB_ESTATE on a
  * handle created without the bit.  nb_collision_stats synchronises and returns the pairs of the last step, the pairs resolved
  * since creation, the resolution rounds of the last step (ready pairs are resolved together; a chain of k touching discs
@@ -480,7 +521,7 @@ int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, uint64_t *ove
 
 /* The reference's `quadtree.nodes` (Quadtree.hpp:14; copied by its caller every frame, main.cpp:626, and drawn by
  * drawQuadtreeNode, main.cpp:394-475): the tree of the MOST RECENT BUILD on the handle as Node records.  The most recent build is
- * the force evaluation of the last nb_step / nb_accelerations, or an nb_energy on a NB_FLAG_TREE_ENERGY handle; after nb_step that
+ * the force evaluation of the last nb_step / nb_accelerations, or an nb_energy / nb_potentials on a NB_FLAG_TREE_ENERGY handle; after nb_step that
  * is the tree of the positions BEFORE the drift, as the reference's quadtree.nodes after step().  Any tree handle, any of the four
  * tree flags, either rsqrt mode: the tree does not depend on them (quadrupole moments are not exported: Node has no field).
  * REFERENCE FORM (the reference's own indices follow the insertion order and cannot be reproduced; this is the one numbering with

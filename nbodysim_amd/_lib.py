@@ -202,6 +202,7 @@ PROTOTYPES = {
     "nb_accelerations": (C.c_int, [C.c_void_p]),
     "nb_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nb_momentum": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "nb_potentials": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nb_collide_capacity": (C.c_int, [C.c_void_p, C.c_size_t]),
     "nb_collision_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "nb_tree_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),

@@ -1,6 +1,7 @@
 // nb_sim.hip.h — the handle behind the C ABI, and what every piece of host code around it needs: the HIP error check, the
 // device binding, the dispatchers from run-time choices to template arguments.  Included by nb_capi.hip (the one device
-// translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h and nb_raster_host.hip.h.
+// translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h, nb_raster_host.hip.h and
+// nb_potential_host.hip.h.
 #pragma once
 #include "nbody.h"
 #include "nbody_debug.h"
@@ -10,6 +11,7 @@
 #include "nb_collide.hip.h"
 #include "nb_tree.hip.h"
 #include "nb_raster.hip.h"
+#include "nb_potential.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -90,6 +92,7 @@ struct nb_sim {
     hipEvent_t ev_bounce[4] = {nullptr, nullptr, nullptr, nullptr};   // one per slot / per staged piece
     double *ered_dev = nullptr;     // energy partials
     double *pred_dev = nullptr;     // momentum partials (nb_momentum), allocated on first use
+    double *phi_dev = nullptr;      // i_count potentials (nb_potentials), allocated on first use
     size_t ered_blocks = 0;
 
     // launch geometry (per job: particles per lane and j-slices)

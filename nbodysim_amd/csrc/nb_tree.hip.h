@@ -689,8 +689,11 @@ __device__ __forceinline__ void tree_energy_of(uint32_t b, double phi, const flo
     u = 0.5 * m * phi;
 }
 
+// EMIT (nb_potentials): the walker's phi is the result.  It is stored to usum[body] (usum is then an array of n doubles by body
+// index, ksum is not used) and nothing is reduced; the massless bodies walk too, alone as in the force walk: no partner on their
+// position is added (they are not in a sorted run), and a leaf exactly under them gives no term (d^2 = 0).
 // the lanes tree_lane_alone takes out of their windows, massless ones excepted: the per-lane walk of tree_walk_one<.., true, QUAD>
-template <bool QUAD, bool REL>
+template <bool QUAD, bool REL, bool EMIT = false>
 __global__ __launch_bounds__(256)
 void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                           const float2 *__restrict__ pos, const float2 *__restrict__ vel, const float *__restrict__ mass, uint32_t n,
@@ -701,7 +704,7 @@ void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restr
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     double k = 0.0, u = 0.0;
-    if (i < n && !st->fail && i < st->massive && tree_lane_alone(i, head, uidx, ufirst, st)) {
+    if (i < n && !st->fail && (EMIT || i < st->massive) && tree_lane_alone(i, head, uidx, ufirst, st)) {
         const uint32_t b = val[i];
         const float2 p = pos[b];
         const uint32_t total = (uint32_t)st->nodes;
@@ -734,16 +737,17 @@ void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restr
                 node = node + 1u;
             }
         }
-        phi += tree_potential_shared(i, val, mass, head, uidx, ufirst, st, eps2);
-        tree_energy_of(b, phi, vel, mass, k, u);
+        if (!EMIT || i < st->massive) phi += tree_potential_shared(i, val, mass, head, uidx, ufirst, st, eps2);
+        if constexpr (EMIT) usum[b] = phi;
+        else tree_energy_of(b, phi, vel, mass, k, u);
     }
-    tree_energy_reduce(k, u, ksum, usum);
+    if constexpr (!EMIT) tree_energy_reduce(k, u, ksum, usum);
 }
 
 // the windows: tree_walk_group's loop (node index through readfirstlane, one ballot, the moment record loaded inside the
 // wave-uniform accepted-branch path).  The lanes that take no part stay out of the loop, so they neither vote nor lead, and
 // join the block reduction with zeros.
-template <bool QUAD, bool REL>
+template <bool QUAD, bool REL, bool EMIT = false>
 __global__ __launch_bounds__(256)
 void tree_potential_group(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const uint32_t *__restrict__ val,
                           const float2 *__restrict__ pos, const float2 *__restrict__ vel, const float *__restrict__ mass, uint32_t n,
@@ -792,9 +796,10 @@ void tree_potential_group(const float4 *__restrict__ nd, const uint32_t *__restr
             node = all_far && next > node ? next : node + 1u;    // (a leaf's next is node + 1)
         }
         phi += tree_potential_shared(i, val, mass, head, uidx, ufirst, st, eps2);
-        tree_energy_of(b, phi, vel, mass, k, u);
+        if constexpr (EMIT) usum[b] = phi;
+        else tree_energy_of(b, phi, vel, mass, k, u);
     }
-    tree_energy_reduce(k, u, ksum, usum);
+    if constexpr (!EMIT) tree_energy_reduce(k, u, ksum, usum);
 }
 
 // Kick and drift with acc[] as written by tree_walk.  A failed build integrates nothing: the positions are carried over.

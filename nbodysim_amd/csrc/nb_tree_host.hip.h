@@ -125,7 +125,9 @@ static int launch_tree_force(nb_sim *s)
 // potential walk (nb_tree.hip.h): the
 // windows into partials [0, g) (K) and [g, 2g) (U), the lanes that left them into [2g, 3g) and [3g, 4g).  Touches neither acc[]
 // nor the state; the tree arrays are this build's afterwards.
-static int launch_tree_potential(nb_sim *s)
+// With `phi` (nb_potentials: n doubles by body index) the same build and walk, EMIT: every walker, the massless ones included, stores
+// its phi there and nothing is reduced; the two walk kernels are then bracketed like a force launch for nb_profile_read.
+static int launch_tree_potential(nb_sim *s, double *phi = nullptr)
 {
     { const int rc = launch_tree_build(s); if (rc) return rc; }
     const uint32_t n = (uint32_t)s->n, g = (n + 255u) / 256u;
@@ -139,6 +141,19 @@ static int launch_tree_potential(nb_sim *s)
     const float *lo = s->bh.lo;
     tree_leaf_residual<<<g, 256, 0, s->stream>>>(s->bh.nd, s->bh.base, s->bh.ufirst, v2, mass, n, st, s->bh.lo);
     const float2 *aprev = (const float2 *)s->acc;           // REL: the predicate of a force evaluation issued now: acc[] of this moment, read only
+    if (phi) {
+        std::pair<hipEvent_t, hipEvent_t> pr;
+        if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
+        with_flags([&](auto quad, auto rel) {
+            tree_potential_group<quad, rel, true><<<g, 256, 0, s->stream>>>(s->bh.nd, s->bh.nx, v2, pos, vel, mass, n, eps2, s->bh.theta2, st,
+                                                                            s->bh.head, s->bh.uidx, s->bh.ufirst, (double *)nullptr, phi, lo, qm, aprev, s->bh.alpha);
+            tree_potential_alone<quad, rel, true><<<g, 256, 0, s->stream>>>(s->bh.nd, s->bh.nx, v2, pos, vel, mass, n, eps2, s->bh.theta2, st,
+                                                                            s->bh.head, s->bh.uidx, s->bh.ufirst, (double *)nullptr, phi, lo, qm, aprev, s->bh.alpha);
+        }, s->bh.quad, tree_rel_active(s));
+        HIPCHK(hipGetLastError());
+        if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
+        return NB_OK;
+    }
     with_flags([&](auto quad, auto rel) {
         tree_potential_group<quad, rel><<<g, 256, 0, s->stream>>>(s->bh.nd, s->bh.nx, v2, pos, vel, mass, n, eps2, s->bh.theta2, st,
                                                                   s->bh.head, s->bh.uidx, s->bh.ufirst, e, e + g, lo, qm, aprev, s->bh.alpha);

@@ -227,6 +227,9 @@ public:
     // on the device at the positions of the work enqueued so far; `bodies` is not refreshed and need not be.  Replaces the per-body draw
     // loop of main.cpp:745-835 by one texture upload.  Either plane may be null, not both; each holds view.width * view.height elements.
     void raster(const nb_view &view, uint32_t *count, float *mass) { check(nb_raster(sim_, &view, count, mass), "nb_raster"); }
+    // The potential of every body (nb_potentials, include/nbody.h) at the positions of the work enqueued so far: phi holds bodies.size()
+    // doubles; with the velocities of `bodies` after step(): binding energy of body i = |vel_i|^2 / 2 + phi[i].
+    void potentials(double *phi) { check(nb_potentials(sim_, phi), "nb_potentials"); }
     nb_sim *handle() { return sim_; }
 
 private:

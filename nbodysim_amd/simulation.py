@@ -228,6 +228,18 @@ class Simulation:
         L.check("nb_momentum", self._lib.nb_momentum(self._h, p, C.byref(lz)), self._lib)
         return (p[0], p[1], p[2]), lz.value
 
+    def potentials(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The potential of every owned body, ``phi_i = -sum_{j != i} m_j / sqrt(r_ij^2 + eps^2)`` (``nb_potentials``; synchronises):
+        float64 of shape ``(i_count,)``; the binding energy of body i is ``v_i^2 / 2 + phi_i``.  ``out``: a writeable C-contiguous
+        float64 array of that shape (one over ``nb_host_alloc`` memory is written by the copy engine directly); default a new array."""
+        if out is None:
+            out = np.empty(self.i_count, dtype=np.float64)
+        elif (not isinstance(out, np.ndarray) or out.dtype != np.float64 or out.shape != (self.i_count,) or not out.flags.c_contiguous
+              or not out.flags.writeable):
+            raise TypeError(f"out must be a writeable C-contiguous ({self.i_count},) numpy array of float64")
+        L.check("nb_potentials", self._lib.nb_potentials(self._h, out.ctypes.data), self._lib)
+        return out
+
     def collision_stats(self) -> dict:
         """Counters of the collision path (``nb_collision_stats``; synchronises): pairs of the last step, pairs resolved since
         creation, resolution rounds of the last step, steps that were over the pair capacity.  All 0 without ``collide``."""
