@@ -592,6 +592,52 @@ typedef struct nb_view {
 } nb_view;
 int nb_raster(nb_sim *s, const nb_view *view, uint32_t *count, float *mass);
 
+/* Who is near every body, how many, and the k nearest: the query behind the reference's drawConnections (main.cpp:233-386: a uniform
+ * grid of MAX_DISTANCE cells, getGridKey :67-78, and up to MAX_CONNECTIONS links per body to the bodies of the 3 x 3 cells round it
+ * with distSq < adaptiveDistanceSq), without nb_sync of 64 B per body and a hash-map pass on the host every frame; also the local
+ * density estimate, the linking step of friends-of-friends and the nearest-neighbour distance of an analysis.  The reference's own
+ * selection (the first 16 bodies per cell in insertion order, the first hits in unordered_map order, truncating cell keys) depends on
+ * the order of the bodies and is not reproduced: this is the one order-independent definition with the same predicate.
+ * WHICH BODIES: the queries are the owned block, nb_owned_count(s) rows, at the positions of all work enqueued so far, exactly as
+ * nb_sync_positions defines them; the candidates are all n bodies of the CURRENT replica (on a sharded handle it must be complete, as
+ * for nb_energy).  An NB_FP64 handle's positions are rounded to float first; a dims = 3 handle is projected on (x, y): nb_raster's
+ * rules.  Every kind of handle: direct or tree, any flags, sharded or not.
+ * PREDICATE: fp32, one rounding per operation, no contraction, the reference's (body1->pos - body2->pos).mag_sq() < adaptiveDistanceSq:
+ *     dx = x_j - x_i      dy = y_j - y_i      d2 = dx * dx + dy * dy      r2 = radius * radius
+ * j is a neighbour of i when j != i && d2 < r2: the self term is left out by index, the comparison is strict, and bodies that share
+ * i's position are its neighbours at d2 = 0.  A body with a non-finite coordinate has no neighbours and is nobody's neighbour (the
+ * predicate is false on NaN and infinity).
+ * OUTPUTS: count[i] = the number of ALL neighbours of owned body i, not capped at k.  Row i of idx holds k entries: the
+ * min(count[i], k) neighbours that come first in ascending order of (d2, j), as global body indices, then NB_NO_NEIGHBOR; dist2 has
+ * the same shape and holds their d2, then +inf.  Since d2 >= 0 its bits order like its value, so the order is that of the 64-bit
+ * integer (bits(d2) << 32) | j: ties in d2 are broken by the index and the result is unique.  CONSEQUENCES: two handles agree bit for
+ * bit, and permuting the bodies permutes the rows and relabels the indices wherever the kept entries and the first one left out have
+ * distinct d2.  Any of idx / dist2 / count may be NULL, not all three; a plane that is not asked for is not written and not copied.
+ * k is ignored for a count-only call.  The destinations may be any host memory, as for nb_sync: ranges known to be page-locked
+ * (nb_host_alloc / nb_host_register) are written by the copy engine directly, anything else moves through page-locked staging of the
+ * library's.
+ * ERRORS: NB_EINVAL, naming the argument, before any device work: a NULL handle; idx, dist2 and count all NULL; radius not finite or
+ * <= 0; radius * radius (fp32) not finite or equal to 0; k outside 1 .. 32 when idx or dist2 is asked for.  NB_ESTATE while a split
+ * step is in flight.  The call synchronises; a pending once-only report (collision capacity, failed tree build) leaves through it as
+ * through nb_raster (NB_ENOMEM, once), and nothing is written to the destinations then.
+ * Nothing of the handle changes: positions, velocities, acc[], frame counter, tree arrays and nb_tree_stats are untouched (the query
+ * has scratch of its own and does not borrow the tree's key arrays), and the next step is bit-identical to one on a handle that
+ * never called this.
+ * Memory: nothing until the first call; then (growth only, freed by nb_destroy) 40 bytes per body of the replica on the device (the
+ * float position, the cell key and the body index, each by body and in sorted order) plus the sort's temporary storage; 4 bytes per
+ * owned body once a count is asked for; 4 bytes per owned body x k for idx and 4 for dist2, each once asked for, for the largest k
+ * seen; page-locked host staging of the size of the largest plane a destination needed.
+ * Cost: the bodies are sorted by the cell of a grid of cell size radius x (1 + 2^-16) and every query tests the bodies of the 3 x 3
+ * cells round it, so the cost is proportional to the bodies in those cells; a radius that covers the whole system is the n^2 sweep.
+ * The caller chooses the radius.  The search is cooperative: a workgroup stages the candidates of 256 neighbouring queries through LDS.
+ * On an MI355X, Plummer spheres with a radius that gives a mean count of 29 - 31, idx and count (profiles/neighbors_bench.log): at
+ * 1 048 576 bodies k = 5 takes 0.93 ms into nb_host_alloc memory and 1.53 ms into a pageable array (k = 16: 2.04 / 3.76 ms), of which
+ * the search kernel 0.23 ms (0.52) and the sort 0.20 ms; at 262 144 bodies 0.39 / 0.57 ms, at 8 388 608 (tree handle) 6.1 / 10.2 ms;
+ * nb_sync of the same handles takes 0.71 / 2.68 / 21.6 ms.  16 384 bodies in ONE cell: 2.2 ms, 1.2e11 pairs per second.
+ * With nb_profile_enable the search kernel is bracketed like a force launch and counts as one (nb_profile_read). */
+#define NB_NO_NEIGHBOR 0xFFFFFFFFu
+int nb_neighbors(nb_sim *s, float radius, uint32_t k, uint32_t *idx, float *dist2, uint32_t *count);
+
 /* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
  * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without
  * the flag.  At creation alpha is 0.005: GADGET-2's customary ErrTolForceAcc, not a number measured for this library.  A setter

@@ -1,7 +1,7 @@
 // nb_sim.hip.h — the handle behind the C ABI, and what every piece of host code around it needs: the HIP error check, the
 // device binding, the dispatchers from run-time choices to template arguments.  Included by nb_capi.hip (the one device
-// translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h, nb_raster_host.hip.h and
-// nb_potential_host.hip.h.
+// translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h, nb_raster_host.hip.h,
+// nb_potential_host.hip.h and nb_neighbors_host.hip.h.
 #pragma once
 #include "nbody.h"
 #include "nbody_debug.h"
@@ -12,6 +12,7 @@
 #include "nb_tree.hip.h"
 #include "nb_raster.hip.h"
 #include "nb_potential.hip.h"
+#include "nb_neighbors.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -227,6 +228,22 @@ struct nb_sim {
         void *stage = nullptr;                 // page-locked host staging for destinations the library does not know to be page-locked
         uint64_t stage_cap = 0;                // pixels (4 B each) it holds
     } ras;
+
+    // nb_neighbors (nb_neighbors.hip.h): nothing in `nbr` exists before the first call; the tree's key arrays are not borrowed
+    struct Neighbors {
+        uint64_t cap = 0;                      // bodies the six per-body arrays hold: n from the first call on
+        float2 *xy = nullptr, *sxy = nullptr;  // positions rounded to float: by body, in sorted order
+        uint64_t *key = nullptr, *skey = nullptr;   // cell keys: by body, sorted
+        uint32_t *val = nullptr, *sval = nullptr;   // body indices: identity, in sorted order
+        void *tmp = nullptr;                   // rocprim temporary storage of the sort (asked for n pairs)
+        size_t tmp_bytes = 0;
+        uint32_t *cnt = nullptr;               // i_count counts, once a count is asked for
+        uint64_t idx_cap = 0, d2_cap = 0;      // entries (owned bodies x k) the two row planes hold: grown by the largest k seen
+        uint32_t *idx = nullptr;
+        float *d2 = nullptr;
+        void *stage = nullptr;                 // page-locked host staging for destinations the library does not know to be page-locked
+        uint64_t stage_cap = 0;                // bytes it holds: the largest plane that needed it (one plane at a time goes through it)
+    } nbr;
 
     // profiling
     bool prof = false;

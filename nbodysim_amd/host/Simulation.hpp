@@ -230,6 +230,14 @@ public:
     // The potential of every body (nb_potentials, include/nbody.h) at the positions of the work enqueued so far: phi holds bodies.size()
     // doubles; with the velocities of `bodies` after step(): binding energy of body i = |vel_i|^2 / 2 + phi[i].
     void potentials(double *phi) { check(nb_potentials(sim_, phi), "nb_potentials"); }
+    // Who is near every body (nb_neighbors, include/nbody.h), at the positions of the work enqueued so far: for drawConnections
+    // (main.cpp:233-386) call it with MAX_DISTANCE and MAX_CONNECTIONS; row i of idx then holds the k nearest bodies within `radius` of
+    // bodies[i], nearest first, padded with NB_NO_NEIGHBOR; dist2 their squared distances, count[i] all of them.  idx and dist2 hold
+    // bodies.size() * k entries, count bodies.size(); any may be null, not all three.
+    void neighbors(float radius, uint32_t k, uint32_t *idx, float *dist2, uint32_t *count)
+    {
+        check(nb_neighbors(sim_, radius, k, idx, dist2, count), "nb_neighbors");
+    }
     nb_sim *handle() { return sim_; }
 
 private:

@@ -320,6 +320,26 @@ class Simulation:
             return (count if want_count else None), (mass if want_mass else None)
         return count
 
+    def neighbors(self, radius: float, k: int, dist2: bool = False, count: bool = False):
+        """The ``k`` nearest bodies within ``radius`` of every owned body, found on the device (``nb_neighbors``; synchronises): j is a
+        neighbour of i when ``j != i`` and the fp32 ``dx*dx + dy*dy < radius*radius``.  Returns the ``(i_count, k)`` uint32 array of
+        global body indices in ascending order of (d2, index), padded with ``NB_NO_NEIGHBOR``; with ``dist2`` also the float32 d2 of
+        the same shape, padded with +inf; with ``count`` also the uint32 number of ALL neighbours of every owned body, not capped
+        at ``k``: ``idx``, ``(idx, d2)``, ``(idx, count)`` or ``(idx, d2, count)``.  ``k = 0`` is the count-only call and returns
+        the counts alone."""
+        if not 0 <= k <= 32:
+            raise ValueError(f"neighbors: k must be 1 .. 32, or 0 for the counts alone (got {k})")
+        rows = k > 0
+        idx = np.empty((self.i_count, k), dtype=np.uint32) if rows else None
+        d2 = np.empty((self.i_count, k), dtype=np.float32) if rows and dist2 else None
+        cnt = np.empty(self.i_count, dtype=np.uint32) if count or not rows else None
+        L.check("nb_neighbors", self._lib.nb_neighbors(self._h, radius, k, *(a.ctypes.data if a is not None else None for a in (idx, d2, cnt))),
+                self._lib)
+        if not rows:
+            return cnt
+        out = tuple(a for a in (idx, d2, cnt) if a is not None)
+        return out[0] if len(out) == 1 else out
+
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
         L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)
