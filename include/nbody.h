@@ -638,6 +638,52 @@ int nb_raster(nb_sim *s, const nb_view *view, uint32_t *count, float *mass);
 #define NB_NO_NEIGHBOR 0xFFFFFFFFu
 int nb_neighbors(nb_sim *s, float radius, uint32_t k, uint32_t *idx, float *dist2, uint32_t *count);
 
+/* Which bodies form a clump: the friends-of-friends groups of the bodies at linking length `radius`, the standard group finder of
+ * N-body work, found on the device; the answer is 4 bytes per body.  Without it a caller copies out neighbour rows (k <= 32 truncates
+ * the link graph in any dense region) or nb_syncs 64 B per body and runs a union-find on the host every frame.  With nb_potentials
+ * the most-bound body of a group is its centre.
+ * LINK: bodies i != j are linked when nb_neighbors' predicate holds, word for word: fp32, one rounding per operation, no contraction,
+ *     dx = x_j - x_i      dy = y_j - y_i      d2 = dx * dx + dy * dy      r2 = radius * radius      linked when d2 < r2
+ * The comparison is strict; bodies on one position are linked (d2 = 0); massless bodies take part; a body with a non-finite
+ * coordinate links to nobody.  The relation is symmetric: fp32 subtraction is exactly antisymmetric, so d2(i, j) = d2(j, i) bit for
+ * bit.
+ * WHICH BODIES: nb_neighbors' rules.  The groups are the connected components of that graph over ALL n bodies of the CURRENT replica
+ * (on a sharded handle it must be complete, as for nb_energy), at the positions of all work enqueued so far, exactly as
+ * nb_sync_positions defines them.  An NB_FP64 handle's positions are rounded to float first; a dims = 3 handle is projected on
+ * (x, y).  Every kind of handle: direct or tree, any flags, sharded or not.
+ * OUTPUTS, for the owned block, nb_owned_count(s) rows: label[i] = the smallest global body index in i's group; size[i] = the number
+ * of members of i's group, over all n bodies; *ngroups = the number of groups among all n bodies, singletons included, which is the
+ * number of bodies whose label is their own index.  A body with a non-finite coordinate is a group of its own.  Any of the three may
+ * be NULL, not all three; a plane that is not asked for costs no pass and no copy, and is not written.  CONSEQUENCES: the result is a
+ * function of the bodies and the radius alone, whatever order the device links in; two handles agree bit for bit; permuting the
+ * bodies permutes the partition, and each label is the smallest NEW index of its group.
+ * label and size may be any host memory, as for nb_sync: ranges known to be page-locked (nb_host_alloc / nb_host_register) are
+ * written by the copy engine directly, anything else moves through page-locked staging of the library's.
+ * ERRORS: NB_EINVAL, naming the argument, before any device work: a NULL handle; label, size and ngroups all NULL; radius not finite
+ * or <= 0; radius * radius (fp32) not finite or equal to 0.  NB_ESTATE while a split step is in flight.  The call synchronises; a
+ * pending once-only report (collision capacity, failed tree build) leaves through it as through nb_neighbors (NB_ENOMEM, once), and
+ * nothing is written to the destinations then.  NB_EHIP, nothing written, if the union-find ever left its loop bounds (every loop of
+ * the link kernel is bounded by n + 1; the bound cannot be reached while the structure is a forest).
+ * Nothing of the handle changes: positions, velocities, acc[], frame counter, tree arrays and nb_tree_stats are untouched, and the
+ * next step is bit-identical to one on a handle that never called this.  The cells, the sort and the staging are the scratch of
+ * nb_neighbors: the two calls may alternate on one handle at any radii.
+ * Memory: nothing until the first call; then (growth only, freed by nb_destroy) nb_neighbors' 40 bytes per body of the replica and
+ * its sort storage, if that call has not made them yet, plus 4 bytes per body of the replica (the union-find, then the labels); 4
+ * bytes per body of the replica and 4 per owned body more once sizes are asked for; page-locked host staging of 4 bytes per owned
+ * body once a destination needs it.
+ * Cost: the bodies are sorted by cell as for nb_neighbors and every unordered pair of bodies in the same or adjacent cells is tested
+ * once (half the pairs nb_neighbors tests); a pair that passes is united in a lock-free union-find (compare-and-swap, no lane waits
+ * for another).  The cost is proportional to the pairs inside adjacent cells: a radius that covers the whole system is the n^2
+ * sweep.  The caller chooses the radius.  What a linked pair costs depends on the partition: cheap while the groups are small, and
+ * dearest when one giant group forms, whose n - 1 hooks each walk to two roots.  On an MI355X, Plummer spheres, all three outputs
+ * into nb_host_alloc memory (profiles/groups_bench.log): at 1 048 576 bodies with a mean of 1 / 5 / 31 links per body (largest
+ * group 192 / 463 238 / 831 606 bodies) 0.60 / 1.25 / 2.71 ms, of which the link kernel 0.11 / 0.67 / 2.14 ms and the sort 0.20 ms,
+ * where nb_neighbors' count-only call takes 0.52 - 0.55 ms; into pageable arrays 0.78 / 1.44 / 2.85 ms; at 262 144 bodies 0.29 /
+ * 0.65 / 0.80 ms; at 8 388 608 (tree handle) 3.33 / 4.97 / 7.72 ms, where nb_sync takes 21.6 ms.  The size pass combines the adds
+ * of a wave and of a workgroup that share a group: all 1 048 576 bodies in ONE group cost it 0.020 ms, one add per body 11.9 ms.
+ * With nb_profile_enable the link kernel is bracketed like a force launch and counts as one (nb_profile_read). */
+int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *size, uint64_t *ngroups);
+
 /* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
  * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without
  * the flag.  At creation alpha is 0.005: GADGET-2's customary ErrTolForceAcc, not a number measured for this library.  A setter

@@ -542,6 +542,7 @@ static int fence_foreign_work(nb_sim *s)
 #include "nb_raster_host.hip.h"
 #include "nb_potential_host.hip.h"
 #include "nb_neighbors_host.hip.h"
+#include "nb_groups_host.hip.h"
 
 // what every synchronising call reports once: a collision step over capacity, a failed tree build
 static int step_check(nb_sim *s)

@@ -1,0 +1,96 @@
+// nb_groups_host.hip.h — host side of nb_groups (kernels: nb_groups.hip.h).  Included by nb_capi.hip behind the neighbours' host, whose
+// front half it shares: neighbors_alloc for the per-body arrays, the sort's storage and the staging, neighbors_cells for the keys, the
+// sort and the gather.  It moves its planes with copy_d2h / pinned_covers like nb_neighbors.
+#pragma once
+
+#ifdef NB_GROUPS_PLAIN_TALLY                   // A/B builds (tools/groups_bench.py): one global add per body in the size pass
+constexpr bool GROUPS_COMBINE = false;
+#else
+constexpr bool GROUPS_COMBINE = true;
+#endif
+
+// Scratch of its own, beside nb_neighbors' 40 B per body and sort storage: 4 B per body of the replica (parent[], then the labels)
+// from the first call on; 4 B per body of the replica (member counts) and 4 B per owned body (the size plane) once sizes are asked
+// for; two words on the device and two page-locked ones (fault word, number of groups).  Growth only.
+static int groups_alloc(nb_sim *s, bool want_size)
+{
+    nb_sim::Groups &g = s->grp;
+    const size_t n = s->n;
+    const bool grow_s = want_size && !g.size;
+    if (g.cap >= n && g.words && g.host && !grow_s) return NB_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (g.cap < n) {                                             // (a first attempt that ran out of memory half way left some of them)
+        s->pool.release(g.parent);
+        HIPCHK(s->pool.alloc(g.parent, n));
+        g.cap = n;
+    }
+    if (!g.words) HIPCHK(s->pool.alloc(g.words, 2));
+    if (!g.host) HIPCHK(s->pool.alloc_pinned(g.host, 2));
+    if (grow_s) {
+        s->pool.release(g.cnt);
+        HIPCHK(s->pool.alloc(g.cnt, n));
+        HIPCHK(s->pool.alloc(g.size, s->i_count));
+    }
+    return NB_OK;
+}
+
+// Which bodies form a clump: the friends-of-friends groups at linking length `radius`, labelled by their smallest body index.
+extern "C" int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *size, uint64_t *ngroups)
+{
+    if (!s) return nb_fail(NB_EINVAL, "nb_groups: NULL handle");
+    if (!label && !size && !ngroups) return nb_fail(NB_EINVAL, "nb_groups: label, size and ngroups are all NULL");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return nb_fail(NB_EINVAL, "nb_groups: radius must be finite and > 0 (got %g)", (double)radius);
+    const float r2 = radius * radius;                             // one fp32 rounding: the kernel's operand
+    if (!std::isfinite(r2) || r2 == 0.0f)
+        return nb_fail(NB_EINVAL, "nb_groups: radius * radius must be finite and > 0 in float (radius %g gives %g)", (double)radius, (double)r2);
+    if (s->in_step) return nb_fail(NB_ESTATE, "nb_groups: a split step is in flight");
+    if (bind(s)) return NB_EHIP;
+    // no snapshot_wait(), as in nb_neighbors
+    { const int rc = step_check(s); if (rc) return rc; }          // synchronises; a pending once-only report leaves through here, nothing written
+    const size_t bytes = s->i_count * sizeof(uint32_t);           // of either plane
+    const bool stage = (label && !pinned_covers(label, bytes)) || (size && !pinned_covers(size, bytes));
+    { const int rc = neighbors_alloc(s, 0, false, false, false, stage ? bytes : 0); if (rc) return rc; }
+    { const int rc = groups_alloc(s, size != nullptr); if (rc) return rc; }
+    nb_sim::Neighbors &q = s->nbr;
+    nb_sim::Groups &g = s->grp;
+    const uint32_t n = (uint32_t)s->n, blocks = (n + BLOCK - 1) / BLOCK, ib = (uint32_t)s->i_begin, ic = (uint32_t)s->i_count;
+    HIPCHK(hipMemsetAsync(g.words, 0, 2 * sizeof(uint32_t), s->stream));
+    { const int rc = neighbors_cells(s, radius); if (rc) return rc; }
+    groups_init<<<blocks, BLOCK, 0, s->stream>>>(g.parent, n);
+    HIPCHK(hipGetLastError());
+    std::pair<hipEvent_t, hipEvent_t> pr;                         // with nb_profile_enable the link kernel counts as one launch
+    if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
+    groups_link<<<blocks, BLOCK, 0, s->stream>>>(q.skey, q.sval, q.sxy, n, r2, g.parent, &g.words[0]);
+    HIPCHK(hipGetLastError());
+    if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
+    groups_flatten<<<blocks, BLOCK, 0, s->stream>>>(g.parent, n, &g.words[0]);
+    HIPCHK(hipGetLastError());
+    if (ngroups) {
+        groups_roots<<<std::min(blocks, 1024u), BLOCK, 0, s->stream>>>(g.parent, n, &g.words[1]);
+        HIPCHK(hipGetLastError());
+    }
+    if (size) {
+        HIPCHK(hipMemsetAsync(g.cnt, 0, (size_t)n * sizeof(uint32_t), s->stream));
+        // workgroups that stay (all of them resident at once): the sum a workgroup carries from batch to batch pays when it sees several
+        const uint32_t tg = GROUPS_COMBINE ? std::max(1u, std::min(blocks, 4u * (uint32_t)s->cus)) : blocks;
+        groups_tally<GROUPS_COMBINE><<<tg, BLOCK, 0, s->stream>>>(g.parent, q.sval, n, g.cnt);
+        HIPCHK(hipGetLastError());
+        groups_sizes<<<(ic + BLOCK - 1) / BLOCK, BLOCK, 0, s->stream>>>(g.parent, g.cnt, ib, ic, g.size);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(g.host, g.words, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (g.host[0])                                                // cannot happen while parent[x] <= x holds (nb_groups.hip.h); nothing is written
+        return nb_fail(NB_EHIP, "nb_groups: the union-find left its bound (%s): parent[] is no forest",
+                       g.host[0] & GROUPS_FAULT_FIND ? "a find of more than n + 1 hops" : "a unite of more than n + 1 rounds");
+    if (label) {
+        const int rc = copy_d2h(s, label, g.parent + ib, bytes, s->stream, pinned_covers(label, bytes) ? nullptr : q.stage);
+        if (rc) return rc;
+    }
+    if (size) {
+        const int rc = copy_d2h(s, size, g.size, bytes, s->stream, pinned_covers(size, bytes) ? nullptr : q.stage);
+        if (rc) return rc;
+    }
+    if (ngroups) *ngroups = g.host[1];
+    return NB_OK;
+}

@@ -66,6 +66,25 @@ static int neighbors_alloc(nb_sim *s, size_t entries, bool want_idx, bool want_d
     return NB_OK;
 }
 
+// The front half that nb_neighbors and nb_groups share: all n bodies of the current replica keyed by the cell of a grid of cell size
+// radius x NEIGHBORS_CELL_SLACK, sorted, their float positions gathered in that order (skey, sval, sxy of `nbr`; neighbors_alloc first).
+static int neighbors_cells(nb_sim *s, float radius)
+{
+    nb_sim::Neighbors &q = s->nbr;
+    const uint32_t n = (uint32_t)s->n, g = (n + BLOCK - 1) / BLOCK;
+    const double inv_h = 1.0 / ((double)radius * NEIGHBORS_CELL_SLACK);
+    with_layout(s, [&](auto L) {
+        using LT = decltype(L);
+        neighbors_keys<LT><<<g, BLOCK, 0, s->stream>>>((const typename LT::vec *)s->pos[s->cur], n, inv_h, q.xy, q.key, q.val);
+    });
+    HIPCHK(hipGetLastError());
+    size_t tmp = q.tmp_bytes;
+    HIPCHK(nb_tree_sort_pairs(q.tmp, tmp, q.key, q.skey, q.val, q.sval, n, s->stream));
+    neighbors_gather<<<g, BLOCK, 0, s->stream>>>(q.xy, q.sval, n, q.sxy);
+    HIPCHK(hipGetLastError());
+    return NB_OK;
+}
+
 // The reference's drawConnections (main.cpp:233-386) without the copy of all bodies and the host's hash-map pass: who is near every
 // body, how many, and the k nearest of them.
 extern "C" int nb_neighbors(nb_sim *s, float radius, uint32_t k, uint32_t *idx, float *dist2, uint32_t *count)
@@ -90,16 +109,7 @@ extern "C" int nb_neighbors(nb_sim *s, float radius, uint32_t k, uint32_t *idx, 
     { const int rc = neighbors_alloc(s, entries, idx != nullptr, dist2 != nullptr, count != nullptr, stage_bytes); if (rc) return rc; }
     nb_sim::Neighbors &q = s->nbr;
     const uint32_t n = (uint32_t)s->n, g = (n + BLOCK - 1) / BLOCK;
-    const double inv_h = 1.0 / ((double)radius * NEIGHBORS_CELL_SLACK);
-    with_layout(s, [&](auto L) {
-        using LT = decltype(L);
-        neighbors_keys<LT><<<g, BLOCK, 0, s->stream>>>((const typename LT::vec *)s->pos[s->cur], n, inv_h, q.xy, q.key, q.val);
-    });
-    HIPCHK(hipGetLastError());
-    size_t tmp = q.tmp_bytes;
-    HIPCHK(nb_tree_sort_pairs(q.tmp, tmp, q.key, q.skey, q.val, q.sval, n, s->stream));
-    neighbors_gather<<<g, BLOCK, 0, s->stream>>>(q.xy, q.sval, n, q.sxy);
-    HIPCHK(hipGetLastError());
+    { const int rc = neighbors_cells(s, radius); if (rc) return rc; }
     std::pair<hipEvent_t, hipEvent_t> pr;                         // with nb_profile_enable the search counts as one launch
     if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
     uint32_t *di = idx ? q.idx : nullptr, *dc = count ? q.cnt : nullptr;

@@ -1,7 +1,7 @@
 // nb_sim.hip.h — the handle behind the C ABI, and what every piece of host code around it needs: the HIP error check, the
 // device binding, the dispatchers from run-time choices to template arguments.  Included by nb_capi.hip (the one device
 // translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h, nb_raster_host.hip.h,
-// nb_potential_host.hip.h and nb_neighbors_host.hip.h.
+// nb_potential_host.hip.h, nb_neighbors_host.hip.h and nb_groups_host.hip.h.
 #pragma once
 #include "nbody.h"
 #include "nbody_debug.h"
@@ -13,6 +13,7 @@
 #include "nb_raster.hip.h"
 #include "nb_potential.hip.h"
 #include "nb_neighbors.hip.h"
+#include "nb_groups.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -244,6 +245,16 @@ struct nb_sim {
         void *stage = nullptr;                 // page-locked host staging for destinations the library does not know to be page-locked
         uint64_t stage_cap = 0;                // bytes it holds: the largest plane that needed it (one plane at a time goes through it)
     } nbr;
+
+    // nb_groups (nb_groups.hip.h): nothing in `grp` exists before the first call; the cells, the sort and the staging are `nbr`'s
+    struct Groups {
+        uint64_t cap = 0;                      // bodies `parent` holds: n from the first call on
+        uint32_t *parent = nullptr;            // the union-find by body index; after the flatten pass the labels of all n
+        uint32_t *cnt = nullptr;               // n member counts by label, once sizes are asked for ...
+        uint32_t *size = nullptr;              // ... and the i_count sizes of the owned block
+        uint32_t *words = nullptr;             // device: the fault word, the number of groups
+        uint32_t *host = nullptr;              // page-locked mirror of the two
+    } grp;
 
     // profiling
     bool prof = false;

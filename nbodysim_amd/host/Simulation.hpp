@@ -238,6 +238,13 @@ public:
     {
         check(nb_neighbors(sim_, radius, k, idx, dist2, count), "nb_neighbors");
     }
+    // Which bodies form a clump (nb_groups, include/nbody.h), at the positions of the work enqueued so far: the friends-of-friends
+    // groups at linking length `radius`.  label[i] is the smallest index of the group of bodies[i], size[i] its member count, *ngroups
+    // the number of groups; label and size hold bodies.size() entries; any may be null, not all three.
+    void groups(float radius, uint32_t *label, uint32_t *size, uint64_t *ngroups)
+    {
+        check(nb_groups(sim_, radius, label, size, ngroups), "nb_groups");
+    }
     nb_sim *handle() { return sim_; }
 
 private:

@@ -340,6 +340,21 @@ class Simulation:
         out = tuple(a for a in (idx, d2, cnt) if a is not None)
         return out[0] if len(out) == 1 else out
 
+    def groups(self, radius: float, size: bool = False, ngroups: bool = False):
+        """The friends-of-friends groups of the bodies at linking length ``radius``, found on the device (``nb_groups``;
+        synchronises): i and j are linked when ``j != i`` and the fp32 ``dx*dx + dy*dy < radius*radius``; the groups are the
+        connected components over all n bodies.  Returns the ``(i_count,)`` uint32 labels of the owned block, each the smallest
+        global body index of its group; with ``size`` also the uint32 member count of every owned body's group; with ``ngroups``
+        also the number of groups among all n bodies as an int: ``label``, ``(label, size)``, ``(label, ngroups)`` or
+        ``(label, size, ngroups)``."""
+        label = np.empty(self.i_count, dtype=np.uint32)
+        sizes = np.empty(self.i_count, dtype=np.uint32) if size else None
+        count = C.c_uint64(0)
+        L.check("nb_groups", self._lib.nb_groups(self._h, radius, label.ctypes.data, sizes.ctypes.data if size else None,
+                                                 C.byref(count) if ngroups else None), self._lib)
+        out = (label,) + ((sizes,) if size else ()) + ((int(count.value),) if ngroups else ())
+        return out[0] if len(out) == 1 else out
+
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
         L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)
