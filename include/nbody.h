@@ -539,13 +539,14 @@ int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, uint64_t *ove
  * out; before any build *count = 0, NB_OK.  NB_ESTATE on a NB_FORCE_DIRECT handle.  A pending failed-build report (node capacity,
  * depth cap) is delivered by this call like by nb_wait: NB_ENOMEM, once; while the last build is a failed one, later calls return
  * NB_ESTATE ("no tree to export").  out may be any host memory, as for nb_sync: ranges known to be page-locked (nb_host_alloc /
- * nb_host_register) are written by the copy engine directly, anything else moves through a page-locked staging buffer of the
- * library's.  Nothing of the handle changes: tree arrays, acc[], positions, velocities, frame counter and nb_tree_stats are
+ * nb_host_register) are written by the copy engine directly, anything else moves through the page-locked staging buffer that the
+ * query calls of a handle share (nb_tree_nodes, nb_raster, nb_neighbors, nb_groups: one buffer, as large as the largest plane any of
+ * them had to stage; one plane at a time goes through it).  Nothing of the handle changes: tree arrays, acc[], positions, velocities, frame counter and nb_tree_stats are
  * untouched, and the next force evaluation is bit-identical to one on a handle that never called this.
  * Memory: nothing until the first call with out != NULL; then, sized by the node count of the build exported (growth only, freed by
  * nb_destroy; NOT by the node capacity 16 n + 4096): 144 bytes per node on the device (the record 128, branch flag 4, branch rank 8,
- * export index 4) plus the scan's temporary storage, and 128 bytes per node of page-locked host staging once a destination needs
- * it.  With nb_profile_enable the export kernels are bracketed like a force launch and count as one (nb_profile_read). */
+ * export index 4) plus the scan's temporary storage; the shared staging buffer is grown to 128 bytes per node once a destination
+ * needs it.  With nb_profile_enable the export kernels are bracketed like a force launch and count as one (nb_profile_read). */
 int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size_t *count);
 
 /* The frame whose size is the screen's: how many bodies, and how much mass, fall into each pixel of a view, binned on the device and
@@ -567,7 +568,8 @@ int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size_t *count);
  * two handles agree bit for bit, and permuting the bodies leaves both planes unchanged bit for bit.
  * Either of count / mass may be NULL, not both; a plane that is not asked for costs no pass and no copy, and is not written.  The
  * destinations (width * height elements each) may be any host memory, as for nb_sync: ranges known to be page-locked (nb_host_alloc /
- * nb_host_register) are written by the copy engine directly, anything else moves through page-locked staging of the library's.
+ * nb_host_register) are written by the copy engine directly, anything else moves through the query calls' shared staging buffer
+ * (nb_tree_nodes).
  * ERRORS: NB_EINVAL, naming the field, before any device work: NULL handle, view or both planes; struct_size != sizeof(nb_view);
  * width or height 0 or above 16384, or width * height > 2^24; scale not finite or <= 0; a non-finite centre; _reserved0 != 0;
  * mass != NULL with mass_quantum not finite or <= 0.  NB_ESTATE while a split step is in flight.  The call synchronises; a pending
@@ -576,8 +578,8 @@ int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size_t *count);
  * Nothing of the handle changes: positions, velocities, acc[], frame counter, tree arrays and nb_tree_stats are untouched, and the
  * next step is bit-identical to one on a handle that never called this.
  * Memory: nothing until the first call; then, per pixel of the largest view seen (growth only, freed by nb_destroy): 4 bytes on the
- * device for the counts; 8 + 4 bytes more (unit sums, float plane) once a mass plane is asked for; 4 bytes of page-locked host staging
- * once a destination needs it: 4 / 12 / 4 MiB for a 1024 x 1024 view.  Cost: adds that share a pixel are combined inside the wave and
+ * device for the counts; 8 + 4 bytes more (unit sums, float plane) once a mass plane is asked for: 4 / 12 MiB for a 1024 x 1024 view;
+ * the shared staging buffer is grown to 4 bytes per pixel (4 MiB) once a destination needs it.  Cost: adds that share a pixel are combined inside the wave and
  * inside the workgroup (LDS) before they reach memory, so the worst case for atomics, every body in ONE pixel, is not the slow one:
  * on an MI355X the bin pass of a 1024 x 1024 view at scale 1e-3 (all bodies in the four pixels round the centre) takes 0.052 ms at
  * 1 048 576 bodies and 0.066 ms (counts) / 0.123 ms (both planes) at 8 388 608, where one global add per body takes 3.1 ms at
@@ -614,8 +616,8 @@ int nb_raster(nb_sim *s, const nb_view *view, uint32_t *count, float *mass);
  * bit, and permuting the bodies permutes the rows and relabels the indices wherever the kept entries and the first one left out have
  * distinct d2.  Any of idx / dist2 / count may be NULL, not all three; a plane that is not asked for is not written and not copied.
  * k is ignored for a count-only call.  The destinations may be any host memory, as for nb_sync: ranges known to be page-locked
- * (nb_host_alloc / nb_host_register) are written by the copy engine directly, anything else moves through page-locked staging of the
- * library's.
+ * (nb_host_alloc / nb_host_register) are written by the copy engine directly, anything else moves through the query calls' shared
+ * staging buffer (nb_tree_nodes).
  * ERRORS: NB_EINVAL, naming the argument, before any device work: a NULL handle; idx, dist2 and count all NULL; radius not finite or
  * <= 0; radius * radius (fp32) not finite or equal to 0; k outside 1 .. 32 when idx or dist2 is asked for.  NB_ESTATE while a split
  * step is in flight.  The call synchronises; a pending once-only report (collision capacity, failed tree build) leaves through it as
@@ -626,7 +628,7 @@ int nb_raster(nb_sim *s, const nb_view *view, uint32_t *count, float *mass);
  * Memory: nothing until the first call; then (growth only, freed by nb_destroy) 40 bytes per body of the replica on the device (the
  * float position, the cell key and the body index, each by body and in sorted order) plus the sort's temporary storage; 4 bytes per
  * owned body once a count is asked for; 4 bytes per owned body x k for idx and 4 for dist2, each once asked for, for the largest k
- * seen; page-locked host staging of the size of the largest plane a destination needed.
+ * seen; the shared staging buffer is grown to the largest plane a destination needs.
  * Cost: the bodies are sorted by the cell of a grid of cell size radius x (1 + 2^-16) and every query tests the bodies of the 3 x 3
  * cells round it, so the cost is proportional to the bodies in those cells; a radius that covers the whole system is the n^2 sweep.
  * The caller chooses the radius.  The search is cooperative: a workgroup stages the candidates of 256 neighbouring queries through LDS.
@@ -658,19 +660,19 @@ int nb_neighbors(nb_sim *s, float radius, uint32_t k, uint32_t *idx, float *dist
  * function of the bodies and the radius alone, whatever order the device links in; two handles agree bit for bit; permuting the
  * bodies permutes the partition, and each label is the smallest NEW index of its group.
  * label and size may be any host memory, as for nb_sync: ranges known to be page-locked (nb_host_alloc / nb_host_register) are
- * written by the copy engine directly, anything else moves through page-locked staging of the library's.
+ * written by the copy engine directly, anything else moves through the query calls' shared staging buffer (nb_tree_nodes).
  * ERRORS: NB_EINVAL, naming the argument, before any device work: a NULL handle; label, size and ngroups all NULL; radius not finite
  * or <= 0; radius * radius (fp32) not finite or equal to 0.  NB_ESTATE while a split step is in flight.  The call synchronises; a
  * pending once-only report (collision capacity, failed tree build) leaves through it as through nb_neighbors (NB_ENOMEM, once), and
  * nothing is written to the destinations then.  NB_EHIP, nothing written, if the union-find ever left its loop bounds (every loop of
  * the link kernel is bounded by n + 1; the bound cannot be reached while the structure is a forest).
  * Nothing of the handle changes: positions, velocities, acc[], frame counter, tree arrays and nb_tree_stats are untouched, and the
- * next step is bit-identical to one on a handle that never called this.  The cells, the sort and the staging are the scratch of
+ * next step is bit-identical to one on a handle that never called this.  The cells and the sort are the scratch of
  * nb_neighbors: the two calls may alternate on one handle at any radii.
  * Memory: nothing until the first call; then (growth only, freed by nb_destroy) nb_neighbors' 40 bytes per body of the replica and
  * its sort storage, if that call has not made them yet, plus 4 bytes per body of the replica (the union-find, then the labels); 4
- * bytes per body of the replica and 4 per owned body more once sizes are asked for; page-locked host staging of 4 bytes per owned
- * body once a destination needs it.
+ * bytes per body of the replica and 4 per owned body more once sizes are asked for; the shared staging buffer is grown to 4 bytes
+ * per owned body once a destination needs it.
  * Cost: the bodies are sorted by cell as for nb_neighbors and every unordered pair of bodies in the same or adjacent cells is tested
  * once (half the pairs nb_neighbors tests); a pair that passes is united in a lock-free union-find (compare-and-swap, no lane waits
  * for another).  The cost is proportional to the pairs inside adjacent cells: a radius that covers the whole system is the n^2

@@ -536,6 +536,41 @@ static int fence_foreign_work(nb_sim *s)
     return NB_OK;
 }
 
+// ---- what the query calls (nb_tree_nodes, nb_raster, nb_potentials, nb_neighbors, nb_groups) share ----
+static int snapshot_wait(nb_sim *s);
+
+// The opening of a query call, behind its argument checks: no split step in flight, the device bound, (nb_potentials: the staging
+// buffer of nb_sync back from a pipelined snapshot,) and step_check, which synchronises: a pending once-only report leaves through
+// here with nothing written.
+static int query_enter(nb_sim *s, const char *name, bool wait_snapshot = false)
+{
+    if (s->in_step) return nb_fail(NB_ESTATE, "%s: a split step is in flight", name);
+    if (bind(s)) return NB_EHIP;
+    if (wait_snapshot && snapshot_wait(s)) return nb_last_error_code();
+    return step_check(s);
+}
+
+static int check_radius(const char *name, float radius, float *r2)
+{
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return nb_fail(NB_EINVAL, "%s: radius must be finite and > 0 (got %g)", name, (double)radius);
+    *r2 = radius * radius;                                        // one fp32 rounding: the kernel's operand
+    if (!std::isfinite(*r2) || *r2 == 0.0f)
+        return nb_fail(NB_EINVAL, "%s: radius * radius must be finite and > 0 in float (radius %g gives %g)", name, (double)radius, (double)*r2);
+    return NB_OK;
+}
+
+// Bytes of the query staging buffer a plane of `bytes` for `dst` asks for: none where there is no plane or the copy engine reaches dst.
+static size_t stage_need(const void *dst, size_t bytes) { return dst && !pinned_covers(dst, bytes) ? bytes : 0; }
+
+// Grow the query staging buffer to `bytes`, before the call's kernels are launched.  Nothing is in flight through it: copy_d2h blocks.
+static int query_stage(nb_sim *s, size_t bytes)
+{
+    HIPCHK(s->pool.regrow_pinned(s->qstage_cap, bytes, s->qstage));
+    return NB_OK;
+}
+
+static int copy_plane(nb_sim *s, void *dst, const void *src, size_t bytes) { return copy_d2h(s, dst, src, bytes, s->stream, s->qstage); }
+
 // ---- the subsystems' host code (it moves its data with copy_h2d / copy_d2h above) ----
 #include "nb_collide_host.hip.h"
 #include "nb_tree_host.hip.h"
@@ -550,8 +585,6 @@ static int step_check(nb_sim *s)
     const int rc = collide_check(s);
     return rc ? rc : tree_check(s);
 }
-
-static int snapshot_wait(nb_sim *s);
 
 static int do_upload(nb_sim *s, const nb_body *in)
 {
@@ -1383,8 +1416,7 @@ extern "C" int nb_sync(nb_sim *s, nb_body *out)
     if ((rc = launch_pack(s))) return rc;
     // registered destination: one DMA; pageable destination: staged in pieces, the host copies piece k out while
     // piece k + 1 is still in flight
-    if ((rc = copy_d2h(s, out, s->aos_dev, bytes, s->stream, direct ? nullptr : s->staging))) return rc;
-    return NB_OK;
+    return copy_d2h(s, out, s->aos_dev, bytes, s->stream, s->staging);
 }
 
 extern "C" int nb_sync_positions(nb_sim *s, float *out_xy)

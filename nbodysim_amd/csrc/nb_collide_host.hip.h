@@ -4,10 +4,9 @@
 
 static int collide_alloc_pairs(nb_sim *s, uint64_t cap)
 {
-    s->pool.release(s->coll.adj);
-    s->coll.cap = 0;
-    HIPCHK(s->pool.alloc(s->coll.adj, 2 * cap));    // every pair sits in two rows
-    s->coll.cap = cap;
+    s->coll.cap = 0;                                // not grow-only: nb_collide_capacity may lower it, so this is always a new block
+    HIPCHK(s->pool.regrow(s->coll.cap, 2 * cap, s->coll.adj));    // every pair sits in two rows ...
+    s->coll.cap = cap;                              // ... and the capacity counts pairs
     return NB_OK;
 }
 

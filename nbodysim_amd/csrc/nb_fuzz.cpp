@@ -10,7 +10,8 @@
 // 2. host I/O: write/read round trips, truncated and forged headers (a forged body count must be refused
 //    before any buffer is sized from it), the generators at ragged sizes.
 // 3. memory pool (nb_mem.h) over malloc / free: random allocate / release / regrow / release_all sequences with a backend
-//    that refuses its k-th request; allocations and frees balance, no pointer outlives its block.
+//    that refuses its k-th request; allocations and frees balance, no pointer outlives its block.  MemPool::regrow, the
+//    grow-only scratch of the library, also meets a refusal at every request of a set of one to three device or pinned arrays.
 #include <unistd.h>
 
 #include <algorithm>
@@ -282,14 +283,66 @@ struct MallocMem {
     static void free_pinned(void *p) { free_device(p); --pinned_live; }       // a block goes back the way it came
 };
 
-static int fuzz_pool(int cases, std::mt19937 &rng)
+template <typename T>
+static void touch_last(T *p, size_t count) { ((char *)p)[count * sizeof(std::conditional_t<std::is_void_v<T>, char, T>) - 1] = 7; }
+
+// One MemPool::regrow of the set p... and what must hold after it.  A refusal leaves cap == 0 and every pointer null or a live
+// recorded block (the caller's comparison of pool.size() with the backend's balance sees to the latter), and the retry — the backend
+// refuses one request only — succeeds without `misuse`.  Returns the refusals met (0 or 1).
+template <typename... T>
+static int checked_regrow(MemPool<MallocMem> &pool, bool pinned, size_t &cap, size_t want, T *&...p)
 {
+    const size_t had = cap, blocks = pool.size(), held = (size_t)((p != nullptr) + ...);
+    const long asked = MallocMem::requests;
+    int e = pinned ? pool.regrow_pinned(cap, want, p...) : pool.regrow(cap, want, p...);
+    if (had >= want) { REQUIRE(e == MallocMem::ok && cap == had && pool.size() == blocks && MallocMem::requests == asked, "a regrow that had nothing to do"); return 0; }
+    const int refused = e != MallocMem::ok;
+    if (refused) {
+        const size_t got = (size_t)((p != nullptr) + ...);
+        REQUIRE(e == -1 && cap == 0 && got < sizeof...(p) && pool.size() == blocks - held + got, "a refused regrow: error %d, capacity %zu, %zu of %zu arrays", e, cap, got, sizeof...(p));
+        REQUIRE(MallocMem::requests == asked + (long)got + 1, "a refused regrow went on asking");
+        e = pinned ? pool.regrow_pinned(cap, want, p...) : pool.regrow(cap, want, p...);
+    }
+    REQUIRE(e == MallocMem::ok && cap == want && ((p != nullptr) && ...) && pool.size() == blocks - held + sizeof...(p), "regrow: error %d, capacity %zu of %zu", e, cap, want);
+    (touch_last(p, want), ...);                                       // `want` elements each, not bytes
+    return refused;
+}
+
+// Every request a set can reach refused once: growing from nothing (k-th of the first regrow) and from a smaller capacity.
+template <typename... T>
+static int regrow_refusals(bool pinned, T *...p)
+{
+    int refused = 0;
+    for (int from : {0, 1})
+        for (long k = 1; k <= (long)sizeof...(p); ++k) {
+            MallocMem::allocs = MallocMem::frees = MallocMem::requests = MallocMem::pinned_live = MallocMem::fail_at = 0;
+            {
+                MemPool<MallocMem> pool;
+                size_t cap = 0;
+                if (from) REQUIRE(checked_regrow(pool, pinned, cap, 100, p...) == 0 && cap == 100, "first regrow");
+                MallocMem::fail_at = MallocMem::requests + k;
+                REQUIRE(checked_regrow(pool, pinned, cap, 300, p...) == 1, "request %ld of the set was not refused", k);
+                REQUIRE(checked_regrow(pool, pinned, cap, 200, p...) == 0 && cap == 300, "the capacity shrank");
+                REQUIRE((size_t)(MallocMem::allocs - MallocMem::frees) == sizeof...(p) && MallocMem::pinned_live == (pinned ? (long)sizeof...(p) : 0), "live blocks");
+                ++refused;
+            }
+            REQUIRE(MallocMem::allocs == MallocMem::frees && MallocMem::pinned_live == 0 && ((p == nullptr) && ...), "regrow_refusals: %ld allocations, %ld frees", MallocMem::allocs, MallocMem::frees);
+        }
+    return refused;
+}
+
+static int fuzz_pool(int cases, std::mt19937 &rng, int *regrow_refused)
+{
+    {
+        float *a = nullptr; uint64_t *b = nullptr; void *c = nullptr;
+        *regrow_refused = regrow_refusals(false, a) + regrow_refusals(true, c) + regrow_refusals(false, a, b, c) + regrow_refusals(true, b, a);
+    }
     for (int c = 0; c < cases; ++c) {
         MallocMem::allocs = MallocMem::frees = MallocMem::requests = MallocMem::pinned_live = 0;
         MallocMem::fail_at = rng() % 3 ? 1 + (long)(rng() % 40) : 0;
-        uint32_t *slot[12] = {};                                        // the handle's fields: fixed addresses
-        void *raw[4] = {};                                              // byte-sized blocks (void *)
-        size_t live = 0;
+        uint32_t *slot[12] = {};                                        // the handle's fields: fixed addresses; 7 .. 11 belong to the regrow sets
+        void *raw[4] = {};                                              // byte-sized blocks (void *); raw[2] and raw[3] belong to regrow sets
+        size_t live = 0, cap[4] = {};                                   // the sets' capacities
         {
             MemPool<MallocMem> pool;
             auto attempt = [&](auto &p, size_t count, bool pinned) -> bool { // one allocation and what must hold after it; true: a new block
@@ -306,7 +359,7 @@ static int fuzz_pool(int cases, std::mt19937 &rng)
             };
             const int ops = 1 + (int)(rng() % 60);
             for (int k = 0; k < ops; ++k) {
-                const unsigned what = rng() % 10, i = rng() % 12, j = rng() % 4;
+                const unsigned what = rng() % 10, i = rng() % 7, j = rng() % 2;
                 const size_t count = rng() % 5 ? 1 + rng() % 3000 : 0;
                 if (what < 4) {
                     if (attempt(slot[i], count, rng() % 4 == 0) && count) slot[i][count - 1] = 7;           // typed: count elements, not bytes
@@ -318,13 +371,19 @@ static int fuzz_pool(int cases, std::mt19937 &rng)
                     pool.release(slot[i]);
                     REQUIRE(slot[i] == nullptr && pool.size() == before - (had ? 1 : 0), "release");
                     live -= had ? 1 : 0;
-                } else if (what < 9) {                                       // the regrow sites: release, then allocate larger
-                    live -= slot[i] ? 1 : 0;
-                    pool.release(slot[i]);
-                    attempt(slot[i], count + 1 + rng() % 5000, false);
+                } else if (what < 9) {                                       // the library's grow-only scratch: one array, several, device, pinned
+                    const size_t want = rng() % 8 ? 1 + rng() % 5000 : 0, before = pool.size();
+                    switch (rng() % 4) {
+                    case 0: *regrow_refused += checked_regrow(pool, false, cap[0], want, slot[8]); break;
+                    case 1: *regrow_refused += checked_regrow(pool, false, cap[1], want, slot[9], slot[10], raw[3]); break;
+                    case 2: *regrow_refused += checked_regrow(pool, true, cap[2], want, slot[11]); break;
+                    default: *regrow_refused += checked_regrow(pool, true, cap[3], want, raw[2], slot[7]); break;
+                    }
+                    live += pool.size() - before;
                 } else if (rng() % 4 == 0) {
                     pool.release_all();
                     live = 0;
+                    for (size_t &q : cap) q = 0;
                     for (auto *q : slot) REQUIRE(q == nullptr, "release_all left a pointer");
                     for (auto *q : raw) REQUIRE(q == nullptr, "release_all left a pointer");
                     REQUIRE(MallocMem::allocs == MallocMem::frees, "release_all left a block");
@@ -353,7 +412,8 @@ int main(int argc, char **argv)
     fuzz_host(dir, rng);
     fuzz_schedule(cases, rng);
     fuzz_idfile(dir, rng);
-    const int pool_cases = fuzz_pool(cases, rng);
-    std::printf("OK planner_cases=%d seed=%u pool_cases=%d\n", cases, seed, pool_cases);
+    int regrow_refused = 0;
+    const int pool_cases = fuzz_pool(cases, rng, &regrow_refused);
+    std::printf("OK planner_cases=%d seed=%u pool_cases=%d regrow_refusals=%d\n", cases, seed, pool_cases, regrow_refused);
     return 0;
 }

@@ -1,6 +1,6 @@
 // nb_groups_host.hip.h — host side of nb_groups (kernels: nb_groups.hip.h).  Included by nb_capi.hip behind the neighbours' host, whose
-// front half it shares: neighbors_alloc for the per-body arrays, the sort's storage and the staging, neighbors_cells for the keys, the
-// sort and the gather.  It moves its planes with copy_d2h / pinned_covers like nb_neighbors.
+// front half it shares: neighbors_alloc for the per-body arrays and the sort's storage, neighbors_cells for the keys, the sort and the
+// gather.  It opens with query_enter and moves its planes with copy_plane through the query staging buffer, like nb_neighbors.
 #pragma once
 
 #ifdef NB_GROUPS_PLAIN_TALLY                   // A/B builds (tools/groups_bench.py): one global add per body in the size pass
@@ -19,11 +19,7 @@ static int groups_alloc(nb_sim *s, bool want_size)
     const bool grow_s = want_size && !g.size;
     if (g.cap >= n && g.words && g.host && !grow_s) return NB_OK;
     HIPCHK(hipStreamSynchronize(s->stream));
-    if (g.cap < n) {                                             // (a first attempt that ran out of memory half way left some of them)
-        s->pool.release(g.parent);
-        HIPCHK(s->pool.alloc(g.parent, n));
-        g.cap = n;
-    }
+    HIPCHK(s->pool.regrow(g.cap, n, g.parent));
     if (!g.words) HIPCHK(s->pool.alloc(g.words, 2));
     if (!g.host) HIPCHK(s->pool.alloc_pinned(g.host, 2));
     if (grow_s) {
@@ -39,18 +35,13 @@ extern "C" int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *siz
 {
     if (!s) return nb_fail(NB_EINVAL, "nb_groups: NULL handle");
     if (!label && !size && !ngroups) return nb_fail(NB_EINVAL, "nb_groups: label, size and ngroups are all NULL");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return nb_fail(NB_EINVAL, "nb_groups: radius must be finite and > 0 (got %g)", (double)radius);
-    const float r2 = radius * radius;                             // one fp32 rounding: the kernel's operand
-    if (!std::isfinite(r2) || r2 == 0.0f)
-        return nb_fail(NB_EINVAL, "nb_groups: radius * radius must be finite and > 0 in float (radius %g gives %g)", (double)radius, (double)r2);
-    if (s->in_step) return nb_fail(NB_ESTATE, "nb_groups: a split step is in flight");
-    if (bind(s)) return NB_EHIP;
-    // no snapshot_wait(), as in nb_neighbors
-    { const int rc = step_check(s); if (rc) return rc; }          // synchronises; a pending once-only report leaves through here, nothing written
+    float r2;
+    { const int rc = check_radius("nb_groups", radius, &r2); if (rc) return rc; }
+    { const int rc = query_enter(s, "nb_groups"); if (rc) return rc; }        // no snapshot wait, as in nb_neighbors
     const size_t bytes = s->i_count * sizeof(uint32_t);           // of either plane
-    const bool stage = (label && !pinned_covers(label, bytes)) || (size && !pinned_covers(size, bytes));
-    { const int rc = neighbors_alloc(s, 0, false, false, false, stage ? bytes : 0); if (rc) return rc; }
+    { const int rc = neighbors_alloc(s, 0, false, false, false); if (rc) return rc; }
     { const int rc = groups_alloc(s, size != nullptr); if (rc) return rc; }
+    { const int rc = query_stage(s, std::max(stage_need(label, bytes), stage_need(size, bytes))); if (rc) return rc; }
     nb_sim::Neighbors &q = s->nbr;
     nb_sim::Groups &g = s->grp;
     const uint32_t n = (uint32_t)s->n, blocks = (n + BLOCK - 1) / BLOCK, ib = (uint32_t)s->i_begin, ic = (uint32_t)s->i_count;
@@ -84,11 +75,11 @@ extern "C" int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *siz
         return nb_fail(NB_EHIP, "nb_groups: the union-find left its bound (%s): parent[] is no forest",
                        g.host[0] & GROUPS_FAULT_FIND ? "a find of more than n + 1 hops" : "a unite of more than n + 1 rounds");
     if (label) {
-        const int rc = copy_d2h(s, label, g.parent + ib, bytes, s->stream, pinned_covers(label, bytes) ? nullptr : q.stage);
+        const int rc = copy_plane(s, label, g.parent + ib, bytes);
         if (rc) return rc;
     }
     if (size) {
-        const int rc = copy_d2h(s, size, g.size, bytes, s->stream, pinned_covers(size, bytes) ? nullptr : q.stage);
+        const int rc = copy_plane(s, size, g.size, bytes);
         if (rc) return rc;
     }
     if (ngroups) *ngroups = g.host[1];

@@ -1,10 +1,9 @@
 // nb_potential_host.hip.h — host side of nb_potentials (kernels: nb_potential.hip.h; the walk of a NB_FLAG_TREE_ENERGY handle:
-// tree_potential_* <.., EMIT>, nb_tree.hip.h).  Included by nb_capi.hip beside the tree and raster hosts; it moves its result with
-// copy_d2h / pinned_covers through the staging buffer of nb_sync.
+// tree_potential_* <.., EMIT>, nb_tree.hip.h).  Included by nb_capi.hip beside the tree and raster hosts; it opens with query_enter like
+// the other query calls, but moves its result with copy_d2h through the staging buffer of nb_sync, hence the snapshot wait.
 #pragma once
 
 static int ensure_staging(nb_sim *s);     // nb_capi.hip, below: the page-locked i_count x 64 B of nb_sync / nb_sync_positions
-static int snapshot_wait(nb_sim *s);
 
 // The direct sweep into s->phi_dev.  Particles per lane: the largest P that still gives four workgroups per CU (P moves a
 // particle to another lane and changes no operation of its sum: nb_potential.hip.h), so small and sharded handles fill the chip
@@ -42,13 +41,9 @@ extern "C" int nb_potentials(nb_sim *s, double *phi)
 {
     if (!s) return nb_fail(NB_EINVAL, "nb_potentials: NULL handle");
     if (!phi) return nb_fail(NB_EINVAL, "nb_potentials: NULL phi");
-    if (s->in_step) return nb_fail(NB_ESTATE, "nb_potentials: a split step is in flight");
-    if (bind(s)) return NB_EHIP;
-    if (snapshot_wait(s)) return nb_last_error_code();            // the staging buffer may still feed a pipelined snapshot
-    { const int rc = step_check(s); if (rc) return rc; }          // synchronises; a pending once-only report leaves through here, phi untouched
+    { const int rc = query_enter(s, "nb_potentials", true); if (rc) return rc; }   // (the staging buffer may still feed a pipelined snapshot)
     const size_t bytes = s->i_count * sizeof(double);
-    const bool direct = pinned_covers(phi, bytes);
-    if (!direct && ensure_staging(s)) return NB_EHIP;
+    if (stage_need(phi, bytes) && ensure_staging(s)) return NB_EHIP;
     if (!s->phi_dev) HIPCHK(s->pool.alloc(s->phi_dev, s->i_count));
     if (s->bh.energy) {       // the build and the potential walk of nb_energy; a failed build is reported by THIS call, phi untouched
         { const int rc = launch_tree_potential(s, s->phi_dev); if (rc) return rc; }
@@ -57,5 +52,5 @@ extern "C" int nb_potentials(nb_sim *s, double *phi)
         const int rc = launch_potential_sweep(s);
         if (rc) return rc;
     }
-    return copy_d2h(s, phi, s->phi_dev, bytes, s->stream, direct ? nullptr : s->staging);
+    return copy_d2h(s, phi, s->phi_dev, bytes, s->stream, s->staging);
 }

@@ -1,5 +1,5 @@
 // nb_raster_host.hip.h — host side of nb_raster (kernels: nb_raster.hip.h).  Included by nb_capi.hip beside the tree and collide
-// hosts; it moves its planes with copy_d2h / pinned_covers like nb_tree_nodes.
+// hosts; it opens with query_enter and moves its planes with copy_plane through the query staging buffer, like nb_tree_nodes.
 #pragma once
 
 #ifdef NB_RASTER_PLAIN                         // A/B builds (tools/raster_bench.py): one global add per body, no combining
@@ -9,32 +9,15 @@ constexpr bool RASTER_COMBINE = true;
 #endif
 
 // Scratch for a view of `pixels`: 4 B per pixel for the counts, 8 + 4 B for the unit sums and the float plane once a mass plane is
-// asked for, 4 B of page-locked staging once a destination needs it (one plane at a time goes through it).  Growth only.
-static int raster_alloc(nb_sim *s, uint64_t pixels, bool want_count, bool want_mass, bool want_stage)
+// asked for.  Growth only.
+static int raster_alloc(nb_sim *s, uint64_t pixels, bool want_count, bool want_mass)
 {
     nb_sim::Raster &r = s->ras;
-    const bool grow_c = want_count && r.cap < pixels, grow_m = want_mass && r.mass_cap < pixels, grow_s = want_stage && r.stage_cap < pixels;
-    if (!grow_c && !grow_m && !grow_s) return NB_OK;
+    const bool grow_c = want_count && r.cap < pixels, grow_m = want_mass && r.mass_cap < pixels;
+    if (!grow_c && !grow_m) return NB_OK;
     HIPCHK(hipStreamSynchronize(s->stream));
-    if (grow_c) {
-        s->pool.release(r.cnt);
-        r.cap = 0;
-        HIPCHK(s->pool.alloc(r.cnt, (size_t)pixels));
-        r.cap = pixels;
-    }
-    if (grow_m) {
-        s->pool.release(r.units); s->pool.release(r.massf);
-        r.mass_cap = 0;
-        HIPCHK(s->pool.alloc(r.units, (size_t)pixels));
-        HIPCHK(s->pool.alloc(r.massf, (size_t)pixels));
-        r.mass_cap = pixels;
-    }
-    if (grow_s) {
-        s->pool.release(r.stage);
-        r.stage_cap = 0;
-        HIPCHK(s->pool.alloc_pinned(r.stage, (size_t)pixels * sizeof(uint32_t)));
-        r.stage_cap = pixels;
-    }
+    if (grow_c) HIPCHK(s->pool.regrow(r.cap, (size_t)pixels, r.cnt));
+    if (grow_m) HIPCHK(s->pool.regrow(r.mass_cap, (size_t)pixels, r.units, r.massf));
     return NB_OK;
 }
 
@@ -59,14 +42,12 @@ extern "C" int nb_raster(nb_sim *s, const nb_view *view, uint32_t *count, float 
     if (view->_reserved0 != 0) return nb_fail(NB_EINVAL, "nb_raster: view->_reserved0 must be 0 (got %u)", view->_reserved0);
     if (mass && (!std::isfinite(view->mass_quantum) || !(view->mass_quantum > 0.0f)))
         return nb_fail(NB_EINVAL, "nb_raster: view->mass_quantum must be finite and > 0 for a mass plane (got %g)", (double)view->mass_quantum);
-    if (s->in_step) return nb_fail(NB_ESTATE, "nb_raster: a split step is in flight");
-    if (bind(s)) return NB_EHIP;
-    // no snapshot_wait() (nb_sync_positions has one for its staging): a pending snapshot reads aos_dev and never writes pos, and
-    // this call has scratch and staging of its own (nb_tree_nodes skips it for the same reason)
-    { const int rc = step_check(s); if (rc) return rc; }          // synchronises; a pending once-only report leaves through here, planes untouched
+    // no snapshot wait (nb_sync_positions has one for its staging): a pending snapshot reads aos_dev and never writes pos, and the
+    // query calls have scratch and staging of their own
+    { const int rc = query_enter(s, "nb_raster"); if (rc) return rc; }
     const size_t bytes = (size_t)pixels * sizeof(uint32_t);       // of either plane
-    const bool stage = (count && !pinned_covers(count, bytes)) || (mass && !pinned_covers(mass, bytes));
-    { const int rc = raster_alloc(s, pixels, count != nullptr, mass != nullptr, stage); if (rc) return rc; }
+    { const int rc = raster_alloc(s, pixels, count != nullptr, mass != nullptr); if (rc) return rc; }
+    { const int rc = query_stage(s, std::max(stage_need(count, bytes), stage_need(mass, bytes))); if (rc) return rc; }
     nb_sim::Raster &r = s->ras;
     if (count) HIPCHK(hipMemsetAsync(r.cnt, 0, bytes, s->stream));
     if (mass) HIPCHK(hipMemsetAsync(r.units, 0, (size_t)pixels * sizeof(unsigned long long), s->stream));
@@ -96,9 +77,8 @@ extern "C" int nb_raster(nb_sim *s, const nb_view *view, uint32_t *count, float 
         HIPCHK(hipGetLastError());
     }
     if (count) {
-        const int rc = copy_d2h(s, count, r.cnt, bytes, s->stream, pinned_covers(count, bytes) ? nullptr : r.stage);
+        const int rc = copy_plane(s, count, r.cnt, bytes);
         if (rc) return rc;
     }
-    if (mass) return copy_d2h(s, mass, r.massf, bytes, s->stream, pinned_covers(mass, bytes) ? nullptr : r.stage);
-    return NB_OK;
+    return mass ? copy_plane(s, mass, r.massf, bytes) : NB_OK;
 }

@@ -151,6 +151,11 @@ struct nb_sim {
 
     MemPool<HipMem> pool;                      // every device / page-locked block of the handle (not the caller's pos_buffers / acc_buffers)
 
+    // the query calls (nb_tree_nodes, nb_raster, nb_neighbors, nb_groups) share one page-locked staging buffer for destinations the
+    // library does not know to be page-locked: one plane at a time goes through it, and every copy-out blocks (query_stage, nb_capi.hip)
+    void *qstage = nullptr;
+    size_t qstage_cap = 0;                     // bytes it holds: the largest plane any of them had to stage
+
     // hard-sphere collisions (NB_EXTRA_COLLIDE, nb_collide.hip.h): nothing in `coll` is allocated when the bit is off
     bool collide = false;
     struct Collide {
@@ -208,14 +213,12 @@ struct nb_sim {
         // nb_tree_nodes (the export kernels of nb_tree.hip.h): nothing in `exp` exists before the first call; grown by the node count exported
         struct Export {
             uint64_t cap = 0;                  // nodes the four arrays below hold
-            uint4 *rec = nullptr;              // the records, 128 B per node
+            nb_tree_node *rec = nullptr;       // the records, 128 B per node (the kernels write them as eight uint4)
             uint32_t *flag = nullptr;          // 1 where a pre-order node is a branch ...
             uint64_t *rank = nullptr;          // ... and the prefix sum: its rank among the branches
             uint32_t *idx = nullptr;           // export index of a pre-order node
             void *tmp = nullptr;               // rocprim temporary storage of that scan (asked for this element count)
             size_t tmp_bytes = 0;
-            void *stage = nullptr;             // page-locked host staging for destinations the library does not know to be page-locked
-            uint64_t stage_cap = 0;            // nodes it holds
         } exp;
     } bh;
 
@@ -226,8 +229,6 @@ struct nb_sim {
         uint64_t mass_cap = 0;                 // pixels `units` and `massf` hold: nothing before the first mass plane
         unsigned long long *units = nullptr;   // mass in quanta, summed as integers
         float *massf = nullptr;                // the mass plane
-        void *stage = nullptr;                 // page-locked host staging for destinations the library does not know to be page-locked
-        uint64_t stage_cap = 0;                // pixels (4 B each) it holds
     } ras;
 
     // nb_neighbors (nb_neighbors.hip.h): nothing in `nbr` exists before the first call; the tree's key arrays are not borrowed
@@ -242,11 +243,9 @@ struct nb_sim {
         uint64_t idx_cap = 0, d2_cap = 0;      // entries (owned bodies x k) the two row planes hold: grown by the largest k seen
         uint32_t *idx = nullptr;
         float *d2 = nullptr;
-        void *stage = nullptr;                 // page-locked host staging for destinations the library does not know to be page-locked
-        uint64_t stage_cap = 0;                // bytes it holds: the largest plane that needed it (one plane at a time goes through it)
     } nbr;
 
-    // nb_groups (nb_groups.hip.h): nothing in `grp` exists before the first call; the cells, the sort and the staging are `nbr`'s
+    // nb_groups (nb_groups.hip.h): nothing in `grp` exists before the first call; the cells and the sort are `nbr`'s
     struct Groups {
         uint64_t cap = 0;                      // bodies `parent` holds: n from the first call on
         uint32_t *parent = nullptr;            // the union-find by body index; after the flatten pass the labels of all n
@@ -302,7 +301,8 @@ static auto with_lanes(int P, F &&f)
     return f(std::integral_constant<int, 1>{});
 }
 
-// ---- defined in nb_capi.hip below the subsystems' host code, which uses them (as it does copy_h2d / copy_d2h / pinned_covers above it) ----
+// ---- defined in nb_capi.hip below the subsystems' host code, which uses them (as it does copy_h2d / copy_d2h / pinned_covers and the
+// query calls' query_enter / check_radius / stage_need / query_stage / copy_plane above it) ----
 static int prof_begin(nb_sim *s, std::pair<hipEvent_t, hipEvent_t> *pr, hipStream_t st = nullptr);
 static int prof_end(nb_sim *s, const std::pair<hipEvent_t, hipEvent_t> &pr, hipStream_t st = nullptr, uint32_t passes = 1);
 static int step_check(nb_sim *s);       // what every synchronising call reports once: a collision step over capacity, a failed tree build

@@ -215,21 +215,16 @@ extern "C" int nb_tree_stats(nb_sim *s, uint64_t *nodes, uint32_t *max_depth, ui
 // eighth of slack so that a tree that grows a little every frame does not reallocate every frame; never above the node capacity.
 static int tree_export_alloc(nb_sim *s, uint64_t total)
 {
-    if (total <= s->bh.exp.cap) return NB_OK;
+    nb_sim::BarnesHut::Export &x = s->bh.exp;
+    if (total <= x.cap && x.tmp) return NB_OK;                    // (no tmp: an earlier attempt ran out of memory at its last request)
     HIPCHK(hipStreamSynchronize(s->stream));
-    s->pool.release(s->bh.exp.rec); s->pool.release(s->bh.exp.flag); s->pool.release(s->bh.exp.rank); s->pool.release(s->bh.exp.idx);
-    s->pool.release(s->bh.exp.tmp);
-    s->bh.exp.cap = 0;
-    const uint64_t cap = std::max<uint64_t>(total, std::min<uint64_t>(total + total / 8 + 1024, s->bh.cap));
-    HIPCHK(s->pool.alloc(s->bh.exp.rec, cap * (sizeof(nb_tree_node) / sizeof(uint4))));
-    HIPCHK(s->pool.alloc(s->bh.exp.flag, cap));
-    HIPCHK(s->pool.alloc(s->bh.exp.rank, cap));
-    HIPCHK(s->pool.alloc(s->bh.exp.idx, cap));
+    s->pool.release(x.tmp);
+    const uint64_t want = std::max<uint64_t>(total, std::min<uint64_t>(total + total / 8 + 1024, s->bh.cap));
+    HIPCHK(s->pool.regrow(x.cap, (size_t)want, x.rec, x.flag, x.rank, x.idx));
     size_t bytes = 0;
-    HIPCHK(nb_tree_scan(nullptr, bytes, s->bh.exp.flag, s->bh.exp.rank, (size_t)cap, s->stream));
-    s->bh.exp.tmp_bytes = std::max<size_t>(bytes, 256);
-    HIPCHK(s->pool.alloc(s->bh.exp.tmp, s->bh.exp.tmp_bytes));
-    s->bh.exp.cap = cap;
+    HIPCHK(nb_tree_scan(nullptr, bytes, x.flag, x.rank, (size_t)x.cap, s->stream));
+    x.tmp_bytes = std::max<size_t>(bytes, 256);
+    HIPCHK(s->pool.alloc(x.tmp, x.tmp_bytes));
     return NB_OK;
 }
 
@@ -238,9 +233,7 @@ extern "C" int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size
 {
     if (!s || !count) return nb_fail(NB_EINVAL, "nb_tree_nodes: NULL %s", !s ? "handle" : "count");
     if (!s->tree) return nb_fail(NB_ESTATE, "nb_tree_nodes: the handle was created with NB_FORCE_DIRECT");
-    if (s->in_step) return nb_fail(NB_ESTATE, "nb_tree_nodes: a split step is in flight");
-    if (bind(s)) return NB_EHIP;
-    { const int rc = step_check(s); if (rc) return rc; }          // synchronises; a pending failed-build report leaves through here, once
+    { const int rc = query_enter(s, "nb_tree_nodes"); if (rc) return rc; }
     const TreeStats &t = *s->bh.host;
     if (t.fail)
         return nb_fail(NB_ESTATE, "nb_tree_nodes: no tree to export: the last build failed (%s)", t.fail == 1 ? "node capacity" : "depth cap");
@@ -252,13 +245,8 @@ extern "C" int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size
         return nb_fail(NB_EINVAL, "nb_tree_nodes: the tree has %llu nodes, out holds %zu", (unsigned long long)total, capacity);
     { const int rc = tree_export_alloc(s, total); if (rc) return rc; }
     const size_t bytes = (size_t)total * sizeof(nb_tree_node);
-    const bool direct = pinned_covers(out, bytes);
-    if (!direct && s->bh.exp.stage_cap < total) {
-        s->pool.release(s->bh.exp.stage);
-        s->bh.exp.stage_cap = 0;
-        HIPCHK(s->pool.alloc_pinned(s->bh.exp.stage, (size_t)s->bh.exp.cap * sizeof(nb_tree_node)));
-        s->bh.exp.stage_cap = s->bh.exp.cap;
-    }
+    // staging for the whole scratch, slack included: it regrows when the scratch does, not with every tree that is a little larger
+    { const int rc = query_stage(s, stage_need(out, bytes) ? (size_t)s->bh.exp.cap * sizeof(nb_tree_node) : 0); if (rc) return rc; }
     const uint32_t tot = (uint32_t)total;
     const uint32_t g = (uint32_t)std::min<uint64_t>((total + 255u) / 256u, 8u * (uint32_t)s->cus);
     std::pair<hipEvent_t, hipEvent_t> pr;                         // with nb_profile_enable the export kernels count as one launch
@@ -267,13 +255,13 @@ extern "C" int nb_tree_nodes(nb_sim *s, nb_tree_node *out, size_t capacity, size
     HIPCHK(hipGetLastError());
     size_t tmp = s->bh.exp.tmp_bytes;
     HIPCHK(nb_tree_scan(s->bh.exp.tmp, tmp, s->bh.exp.flag, s->bh.exp.rank, (size_t)total, s->stream));
-    tree_export_root<<<1, 64, 0, s->stream>>>(s->bh.nd, s->bh.dp, s->bh.root_dev, tot, s->bh.exp.rec, s->bh.exp.idx);
+    tree_export_root<<<1, 64, 0, s->stream>>>(s->bh.nd, s->bh.dp, s->bh.root_dev, tot, (uint4 *)s->bh.exp.rec, s->bh.exp.idx);
     for (uint32_t level = 0; level < t.max_depth && level < (uint32_t)TREE_DEPTH_CAP; ++level)
-        tree_export_level<<<g, 256, 0, s->stream>>>(s->bh.nd, s->bh.nx, s->bh.dp, s->bh.exp.rank, level, tot, s->bh.exp.rec,
-                                                    s->bh.exp.idx);
+        tree_export_level<<<g, 256, 0, s->stream>>>(s->bh.nd, s->bh.nx, s->bh.dp, s->bh.exp.rank, level, tot,
+                                                    (uint4 *)s->bh.exp.rec, s->bh.exp.idx);
     HIPCHK(hipGetLastError());
     if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
-    return copy_d2h(s, out, s->bh.exp.rec, bytes, s->stream, direct ? nullptr : s->bh.exp.stage);
+    return copy_plane(s, out, s->bh.exp.rec, bytes);
 }
 
 // alpha travels to the walks as a kernel argument: the evaluations enqueued so far keep theirs, the next one takes the new value
