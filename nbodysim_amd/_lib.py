@@ -37,7 +37,9 @@ NB_FLAG_TREE_LEAVES = 4096           # (2048 is unassigned)
 NB_FLAG_TREE_QUADRUPOLE = 8192       # with NB_FORCE_TREE and NB_FLAG_TREE_LEAVES only
 NB_FLAG_TREE_ENERGY = 16384          # with NB_FORCE_TREE and NB_FLAG_TREE_LEAVES only: nb_energy walks the tree
 NB_FLAG_TREE_RELATIVE = 32768        # with NB_FORCE_TREE and NB_FLAG_TREE_LEAVES only: acceleration-relative opening test (nb_tree_alpha)
-NB_NO_NEIGHBOR = 0xFFFFFFFF          # the index that pads a row of nb_neighbors
+NB_FLAG_BODY_ORDER = 131072          # the Morton body order of the symmetric kernel at any size (default: 131 072 .. 262 144 bodies; 65536 is unassigned)
+NB_FLAG_NO_BODY_ORDER = 262144       # never: the caller's order
+NB_NO_NEIGHBOR = 0xFFFFFFFF         # the index that pads a row of nb_neighbors
 
 #: numpy view of the reference's 64-byte ``Body`` record (Body.hpp:6-13, Vec2.hpp:17-20)
 BODY_DTYPE = np.dtype(
@@ -209,6 +211,7 @@ PROTOTYPES = {
     "nb_tree_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "nb_tree_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nb_tree_alpha": (C.c_int, [C.c_void_p, C.c_float]),
+    "nb_body_order": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     "nb_raster": (C.c_int, [C.c_void_p, C.POINTER(nb_view), C.c_void_p, C.c_void_p]),
     "nb_neighbors": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nb_groups": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),

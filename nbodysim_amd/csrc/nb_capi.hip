@@ -101,6 +101,42 @@ static uint32_t sym_tile_of(const nb_params &p, size_t n)
     return n < SYM_WS_MAX_N ? SYM_SB_WS : SYM_SB;
 }
 
+// Body order (nb_order.hip.h): the whole-system symmetric launch sweeps the bodies along a Morton curve instead of in the caller's
+// index order, for the clock the part then holds.  For unsharded 2-D direct-sum handles on the symmetric path, fp32 or fp64, from
+// ORDER_MIN_N bodies on.  Measured on Plummer spheres in index order, order on against off in interleaved rounds on one device
+// (profiles/body_order_ab.log): the force launch is 3.4 % shorter at 262 144 bodies, 3.4 % at 131 072 and 3.1 % at 65 536; the copy of
+// the positions, the redirected gather and a sixteenth of a sort take 29 / 12 / 8 us of that back, which leaves 2.9 % / 2.6 % / 1.3 %
+// of a step.  The smallest gain this kernel has been changed for is 1.4 % of a step: on from 131 072 bodies, off at 65 536.
+// NB_FLAG_NO_BODY_ORDER switches it off; NB_FLAG_BODY_ORDER switches it on at ANY size — and, so that the small systems of the tests
+// reach it, lifts the lower size limit of the symmetric scheme itself (order_forced) where the handle is otherwise eligible.
+// And UP TO ORDER_MAX_N bodies: the order costs accuracy.  The terms a lane adds into one fp32 accumulator over an item are then
+// nearly equal, so their rounding errors are no longer random but of one sign, and they grow with the chunks per item of the plan.
+// Largest error of the accelerations against an fp64 handle, in units of max |a|, order off -> on: 2.6e-7 -> 1.4e-6 at 131 072 bodies
+// (16 chunks per item), 2.9e-7 -> 3.0e-6 at 262 144 (44), 5.5e-7 -> 3.1e-5 at 524 288 (172), 1.1e-6 -> 7.8e-5 at 1 048 576 (684); the
+// momentum sum 2.4e-10 -> 1.3e-8 of sum |m a| at 262 144.  The bar of this project is 2e-5 of max |a|: met to 262 144 bodies with
+// room, missed from 524 288 on, not measured in between.
+constexpr size_t ORDER_MIN_N = 131072, ORDER_MAX_N = 262144;
+
+static bool order_possible(const nb_params &p, size_t n, size_t i_count)
+{
+    return !(p.flags & NB_FLAG_NO_BODY_ORDER) && p.force == NB_FORCE_DIRECT && p.dims != 3 && p.shard_world <= 1 &&
+           !(p.flags & NB_FLAG_SHARD_SINGLE) && i_count == n;
+}
+
+static bool order_forced(const nb_sim *s) { return (s->p.flags & NB_FLAG_BODY_ORDER) && order_possible(s->p, s->n, s->i_count); }
+
+static bool order_wanted(const nb_sim *s)
+{
+    if (s->path != StepPath::SYM || !order_possible(s->p, s->n, s->i_count)) return false;
+    if (s->p.flags & NB_FLAG_BODY_ORDER) return true;
+    // Not by itself where the caller asks for the mass-scaled body (NB_FLAG_MASS_SCALING / _MEASURED): the rounding of its pre-multiplied
+    // position sigma_j x_j is the same for every partner of a travelling body, and along the curve those partners are its neighbours —
+    // the errors add up instead of averaging out.  Measured at 262 144 equal-ish masses: the scaled body is 4.1e-7 of the force scale
+    // from the general one in index order, 7.0e-6 along the curve (above the 2e-6 of the measured rule, which then declines).
+    const bool scaling = (s->p.flags & (NB_FLAG_MASS_SCALING | NB_FLAG_MASS_SCALING_MEASURED)) && !(s->p.flags & NB_FLAG_NO_MASS_SCALING);
+    return s->n >= ORDER_MIN_N && s->n <= ORDER_MAX_N && !scaling;
+}
+
 static bool sym_eligible(const nb_sim *s)
 {
     if (s->p.flags & NB_FLAG_NO_SYMMETRY) return false;
@@ -111,7 +147,7 @@ static bool sym_eligible(const nb_sim *s)
     // their uniform one-chunk-per-wave plans it overtakes the one-sided kernel from ~5 600 bodies on (-4 ... -8 % at 5 632, -14 ... -17 %
     // at 6 144, -24 ... -28 % at 7 168, -32 ... -34 % at 10 000; +1 ... +6 % at 5 120, +25 % at 4 096:
     // profiles/history/r04_small_n_plans.log)
-    if (s->n < (sym_tile_of(s->p, s->n) == SYM_SB_WS ? (size_t)5632 : 8 * (size_t)SYM_SB)) return false;
+    if (!order_forced(s) && s->n < (sym_tile_of(s->p, s->n) == SYM_SB_WS ? (size_t)5632 : 8 * (size_t)SYM_SB)) return false;
     const uint32_t world = s->p.shard_world > 1 ? (uint32_t)s->p.shard_world : 1u;
     // Travelling partials: one element per (tile, later particle) pair the handle evaluates — tiles x n / 2 for a
     // whole system (1 GiB at N = 524 288 fp32, 2 GiB at 1 048 576, 32 GiB at 4 194 304), 1/world of that for a rank.
@@ -578,6 +614,7 @@ static int copy_plane(nb_sim *s, void *dst, const void *src, size_t bytes) { ret
 #include "nb_potential_host.hip.h"
 #include "nb_neighbors_host.hip.h"
 #include "nb_groups_host.hip.h"
+#include "nb_order_host.hip.h"
 
 // what every synchronising call reports once: a collision step over capacity, a failed tree build
 static int step_check(nb_sim *s)
@@ -640,6 +677,7 @@ static int do_upload(nb_sim *s, const nb_body *in)
         HIPCHK(hipGetLastError());
     }
     s->mass_scaled = forced_scaling;
+    if (s->ord.on) { const int rc = order_upload(s); if (rc) return rc; }
     if (s->collide) { const int rc = collide_classify(s, in); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(s->stream));  // `in` may be pageable and freed by the caller
     s->acc_valid = false;
@@ -806,8 +844,9 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     if ((e = s->pool.alloc(s->ered_dev, (s->bh.energy ? 4 : 2) * s->ered_blocks)) != hipSuccess) return fail("allocating energy", e);
 
     s->collide = (p.extras & NB_EXTRA_COLLIDE) != 0;
-    if ((symmetric(s) && plan_sym(s) != NB_OK) || (s->collide && collide_alloc(s) != NB_OK) || (s->tree && tree_alloc(s) != NB_OK) ||
-        do_upload(s, init) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }     // (nb_fail has said why)
+    s->ord.on = order_wanted(s);
+    if ((symmetric(s) && plan_sym(s) != NB_OK) || (s->ord.on && order_alloc(s) != NB_OK) || (s->collide && collide_alloc(s) != NB_OK) ||
+        (s->tree && tree_alloc(s) != NB_OK) || do_upload(s, init) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }     // (nb_fail has said why)
     return s;
 }
 
@@ -912,7 +951,7 @@ static int launch_sym_items(nb_sim *s, uint32_t first, uint32_t count, hipStream
         using real = typename decltype(L)::real;
         using vec = typename decltype(L)::vec;
         const real eps2 = (real)s->p.eps * (real)s->p.eps, umv = um ? (real)s->um_mass : (real)1;
-        const vec *pos = (const vec *)s->pos[s->cur];
+        const vec *pos = (const vec *)sym_positions(s);     // an ordered handle: the sorted copies (nb_order_host.hip.h)
         vec *ss = (vec *)s->sym_slab_s, *sr = (vec *)s->sym_slab_r;
         // the kernels' leading arguments differ by layout: (pos), (pos, mass) or (pos, mass, sigma)
         auto go = [&](auto kernel, auto... lead) { return launch_sym_kernel(s, kernel, count, slot, st, lead..., items, ss, sr, n, eps2, umv); };
@@ -921,15 +960,15 @@ static int launch_sym_items(nb_sim *s, uint32_t first, uint32_t count, hipStream
         else if constexpr (L.dims3)
             return with_flags([&](auto q, auto u, auto pp) { return go(force_sym3_f32<q ? RSQ_QUAKE : RSQ_EXACT, u, pp>, pos); }, quake, um, pairs);
         else if constexpr (std::is_same_v<real, double>)
-            return with_flags([&](auto u) { return go(force_sym_f64<u>, pos, (const double *)s->mass); }, um);
+            return with_flags([&](auto u) { return go(force_sym_f64<u>, pos, (const double *)sym_masses(s)); }, um);
         else
             return with_flags([&](auto q, auto pp, auto ws) {
                 constexpr int RQ = q ? RSQ_QUAKE : RSQ_EXACT;
-                const float *mass = (const float *)s->mass;
-                if (um) return go(force_sym_f32<RQ, MM_UNIFORM, pp, ws>, pos, mass, s->sigma);
+                const float *mass = (const float *)sym_masses(s), *sigma = sym_sigma(s);
+                if (um) return go(force_sym_f32<RQ, MM_UNIFORM, pp, ws>, pos, mass, sigma);
                 if constexpr (RQ == RSQ_EXACT && !pp)           // MM_SCALED: exact rsqrt only (decided at upload), no chunk pairs
-                    if (s->mass_scaled) return go(force_sym_f32<RSQ_EXACT, MM_SCALED, false, ws>, pos, mass, s->sigma);
-                return go(force_sym_f32<RQ, MM_GENERAL, pp, ws>, pos, mass, s->sigma);
+                    if (s->mass_scaled) return go(force_sym_f32<RSQ_EXACT, MM_SCALED, false, ws>, pos, mass, sigma);
+                return go(force_sym_f32<RQ, MM_GENERAL, pp, ws>, pos, mass, sigma);
             }, quake, pairs, s->sym_sb == SYM_SB_WS);
     });
     if (rc) return rc;
@@ -956,8 +995,10 @@ static int launch_gather(nb_sim *s, bool fuse, const uint32_t *lo, const uint32_
                 sym_gather3<real, f><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, cov, n, first, cnt, (vec *)dst, (const vec *)add,
                                                                   pc, pn, vel, acc, h, h, kd);
             else
-                sym_gather<real, f><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, cov, n, first, cnt, (vec *)dst, (const vec *)add,
-                                                                 pc, pn, vel, acc, h, h, extras, kd, s->sym_sb_shift);
+                with_flags([&](auto o) {        // an ordered handle (whole system: first = 0): row k belongs to body perm[k]
+                    sym_gather<real, f, o><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, cov, n, first, cnt, (vec *)dst, (const vec *)add,
+                                                                        pc, pn, vel, acc, h, h, extras, kd, s->sym_sb_shift, o ? s->ord.perm : nullptr);
+                }, s->ord.on);
         }, fuse);
     });
     HIPCHK(hipGetLastError());
@@ -987,8 +1028,9 @@ static int launch_sym_gather_late(nb_sim *s, double dt)
 // Whole-system symmetric force (+ optionally the kick/drift).
 static int launch_force_sym(nb_sim *s, bool fuse_step = false, double dt = 0.0)
 {
-    int rc = launch_sym_items(s, 0, s->sym_items);
-    if (rc) return rc;
+    int rc;
+    if (s->ord.on && (rc = order_prepare(s))) return rc;
+    if ((rc = launch_sym_items(s, 0, s->sym_items))) return rc;
     return launch_sym_gather(s, fuse_step, dt);
 }
 
@@ -1747,7 +1789,7 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
         if (bind(s) || collide_read(s)) return nb_last_error_code();     // the last step's record (an overflow stays unreported)
         resolve = s->coll.host->touched == 0 ? "none" : s->coll.host->lds_last ? "lds" : "global";
     }
-    const int used = snprintf(buf, buflen,
+    int used = snprintf(buf, buflen,
              "n=%zu owned=[%zu,+%zu) %s%s rsqrt=%s sum=%s | force: block=%d waves/i-set=%d i/lane=%d i_tiles=%u j_slices(all)=%u grid=%u tile_j=%d | "
              "two-phase P/slices local=%d/%u remote=%d/%u | uniform_mass=%d mass_scaled=%d mass_scaling_check=%.1e | symmetric=%d tile=%u chunk_pairs=%d items=%u chunks/item=%u late=%u slabs=%.1f+%.1f MiB | CUs=%d",
              s->n, s->i_begin, s->i_count, s->fp64 ? "fp64" : "fp32", s->dims3 ? " 3-D" : "",
@@ -1757,6 +1799,10 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
              s->job_local.P, s->job_local.js, s->job_remote.P, s->job_remote.js, (int)s->uniform_mass, (int)s->mass_scaled, (double)s->mass_scaling_dev,
              (int)symmetric(s), s->sym_sb, (int)sym_uses_pairs(s), s->sym_items, s->sym_L, s->sym_items_late,
              (double)s->sym_info.slab_s_bytes / 1048576.0, (double)s->sym_info.slab_r_bytes / 1048576.0, s->cus);
+    if (used >= 0 && (size_t)used < buflen) {       // the order the symmetric launch sweeps the bodies in: the Morton curve / its re-sort cadence, or the caller's
+        if (s->ord.on) used += snprintf(buf + used, buflen - (size_t)used, " order=morton/%u", s->ord.every);
+        else used += snprintf(buf + used, buflen - (size_t)used, " order=0");
+    }
     if (used >= 0 && (size_t)used < buflen)
         snprintf(buf + used, buflen - (size_t)used, " | collide=%d h=%.6g large=%u capacity=%llu resolve=%s", (int)s->collide, s->coll.h,
                  s->coll.large_n, (unsigned long long)s->coll.cap, resolve);

@@ -1016,7 +1016,9 @@ __device__ __forceinline__ void load_pair(const double2 *__restrict__ p, double2
 // wave-split plans); tile g's stationary rows are
 // [row_lo[g], row_hi[g]), its coverage entries cov[cov_begin[g] .. cov_begin[g + 1]).  Segment bounds are
 // multiples of 64 (or n) and segment offsets even (nb_plan.cpp), so a pair (k, k + 1), k even, is covered together.
-template <typename real, bool FUSE>
+// ORD (ordered handles, nb_order.hip.h: whole systems, k0 = 0): particle k of the launch is the k-th body along the curve, and its
+// velocity, position and acceleration live at the caller's index perm[k]: the sums are as before, the finish is redirected.
+template <typename real, bool FUSE, bool ORD = false>
 __device__ __forceinline__
 void sym_gather_block(uint32_t blk,
                 const typename vec2_of<real>::type *__restrict__ slab_s,
@@ -1030,7 +1032,7 @@ void sym_gather_block(uint32_t blk,
                 typename vec2_of<real>::type *__restrict__ pos_next,
                 typename vec2_of<real>::type *__restrict__ vel,
                 typename vec2_of<real>::type *__restrict__ acc,
-                real dt_kick, real dt_drift, int extras, int flags, uint32_t sb_shift)
+                real dt_kick, real dt_drift, int extras, int flags, uint32_t sb_shift, const uint32_t *__restrict__ perm = nullptr)
 {
     typedef typename vec2_of<real>::type real2;
     __shared__ real2 part[GATHER_Q][GATHER_P];
@@ -1040,7 +1042,9 @@ void sym_gather_block(uint32_t blk,
     // thread f < GATHER_P finishes particle f of the workgroup: its velocity and position are fetched now, beside the sums
     const uint32_t f = threadIdx.x, lf = blk * GATHER_P + f;
     real2 vf, xf; vf.x = vf.y = xf.x = xf.y = 0;
-    if constexpr (FUSE) { if (f < (uint32_t)GATHER_P && lf < kn && (flags & INTEG_KICK)) { vf = vel[lf]; xf = pos_cur[k0 + lf]; } }
+    uint32_t of = lf;                                   // where particle lf's state lives
+    if constexpr (ORD) { if (f < (uint32_t)GATHER_P && lf < kn) of = perm[lf]; }
+    if constexpr (FUSE) { if (f < (uint32_t)GATHER_P && lf < kn && (flags & INTEG_KICK)) { vf = vel[of]; xf = pos_cur[k0 + of]; } }
     if (li < kn) {
         const uint32_t g = k >> sb_shift, loc = k & ((1u << sb_shift) - 1u);
         const uint32_t r0 = row_lo[g], r1 = row_hi[g];
@@ -1086,12 +1090,12 @@ void sym_gather_block(uint32_t blk,
 #pragma unroll
         for (int j = 1; j < GATHER_Q; ++j) { t.x += part[j][f].x; t.y += part[j][f].y; }
         if (base) { const real2 bb = base[lf]; t.x += bb.x; t.y += bb.y; }
-        if constexpr (FUSE) kick_drift_loaded<Layout<real, false>, false>(t, vf, xf, lf, pos_next, vel, acc, k0, dt_kick, dt_drift, extras, flags);
-        else acc_sum[k0 + lf] = t;
+        if constexpr (FUSE) kick_drift_loaded<Layout<real, false>, false>(t, vf, xf, of, pos_next, vel, acc, k0, dt_kick, dt_drift, extras, flags);
+        else acc_sum[k0 + of] = t;
     }
 }
 
-template <typename real, bool FUSE>
+template <typename real, bool FUSE, bool ORD = false>
 __global__ __launch_bounds__(BLOCK)
 void sym_gather(const typename vec2_of<real>::type *__restrict__ slab_s,
                 const typename vec2_of<real>::type *__restrict__ slab_r,
@@ -1104,10 +1108,10 @@ void sym_gather(const typename vec2_of<real>::type *__restrict__ slab_s,
                 typename vec2_of<real>::type *__restrict__ pos_next,
                 typename vec2_of<real>::type *__restrict__ vel,
                 typename vec2_of<real>::type *__restrict__ acc,
-                real dt_kick, real dt_drift, int extras, int flags, uint32_t sb_shift)
+                real dt_kick, real dt_drift, int extras, int flags, uint32_t sb_shift, const uint32_t *__restrict__ perm)
 {
-    sym_gather_block<real, FUSE>(blockIdx.x, slab_s, slab_r, row_lo, row_hi, cov_begin, cov, n, k0, kn, acc_sum, base, pos_cur, pos_next, vel, acc,
-                                 dt_kick, dt_drift, extras, flags, sb_shift);
+    sym_gather_block<real, FUSE, ORD>(blockIdx.x, slab_s, slab_r, row_lo, row_hi, cov_begin, cov, n, k0, kn, acc_sum, base, pos_cur, pos_next, vel, acc,
+                                      dt_kick, dt_drift, extras, flags, sb_shift, perm);
 }
 
 // ---------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // nb_sim.hip.h — the handle behind the C ABI, and what every piece of host code around it needs: the HIP error check, the
 // device binding, the dispatchers from run-time choices to template arguments.  Included by nb_capi.hip (the one device
 // translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h, nb_raster_host.hip.h,
-// nb_potential_host.hip.h, nb_neighbors_host.hip.h and nb_groups_host.hip.h.
+// nb_potential_host.hip.h, nb_neighbors_host.hip.h, nb_groups_host.hip.h and nb_order_host.hip.h.
 #pragma once
 #include "nbody.h"
 #include "nbody_debug.h"
@@ -14,6 +14,7 @@
 #include "nb_potential.hip.h"
 #include "nb_neighbors.hip.h"
 #include "nb_groups.hip.h"
+#include "nb_order.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -254,6 +255,20 @@ struct nb_sim {
         uint32_t *words = nullptr;             // device: the fault word, the number of groups
         uint32_t *host = nullptr;              // page-locked mirror of the two
     } grp;
+
+    // body order of the whole-system symmetric path (nb_order.hip.h): nothing in `ord` is allocated unless `on`
+    struct Order {
+        bool on = false;
+        uint32_t every = NB_ORDER_EVERY;       // force evaluations from one sort to the next
+        uint64_t evals = 0;                    // force evaluations since the last upload: a sort goes ahead of every `every`-th
+        uint32_t *perm = nullptr, *val = nullptr;   // sorted position -> body index; the identity the sort permutes
+        uint64_t *key = nullptr, *skey = nullptr;   // keys by body, sorted
+        void *part = nullptr;                  // ORDER_PARTS partial boxes, 4 reals each
+        void *xs = nullptr, *ms = nullptr;     // positions (every evaluation) and masses (every sort; individual masses only) in sorted order
+        float *sigma_s = nullptr;              // sigma in sorted order, where the handle has a sigma
+        void *tmp = nullptr;                   // rocprim temporary storage of the sort (asked for n pairs)
+        size_t tmp_bytes = 0;
+    } ord;
 
     // profiling
     bool prof = false;

@@ -75,6 +75,7 @@ class Simulation:
         tree_quadrupole: bool = False,
         tree_energy: bool = False,
         tree_alpha: Optional[float] = None,
+        body_order: Optional[bool] = None,
     ):
         """The last arguments (from ``uniform_mass`` on) are ``nb_params.flags`` and the launch-geometry tuning fields
         (0 / True = the library's automatic choice); the library reads no environment variables.  ``mass_scaling``: False / None
@@ -93,7 +94,9 @@ class Simulation:
         ``tree_leaves=True`` only, ValueError otherwise): NB_FLAG_TREE_RELATIVE — a cell is accepted only if it also passes
         m size^2 / d^4 < ``tree_alpha`` |a_prev| with the body's own last acceleration (``theta`` stays the cap; fresh initial
         conditions have a_prev = 0, so call ``accelerations()`` once before stepping to have the test active from step 1);
-        ``set_tree_alpha`` changes it between steps, 0 switches it off.  ``library``: another
+        ``set_tree_alpha`` changes it between steps, 0 switches it off.  ``body_order``: None = the library's rule (the whole-system
+        symmetric kernel sweeps the bodies along a Morton curve at 131 072 .. 262 144 bodies), True = NB_FLAG_BODY_ORDER (at any size), False =
+        NB_FLAG_NO_BODY_ORDER (the caller's order); results differ by summation order only, ``describe()`` says which.  ``library``: another
         build of the library bound with ``_lib.bind`` (the tests' -DNB_TEST_HOOKS build); default the product."""
         if tree_leaves and force != "tree":
             raise ValueError('tree_leaves=True needs force="tree" (NB_FLAG_TREE_LEAVES selects a walk of the Barnes-Hut force)')
@@ -137,7 +140,8 @@ class Simulation:
                       else L.NB_FLAG_NO_MASS_SCALING if mass_scaling is False else 0)
                    | (L.NB_FLAG_STATIC_ITEMS if static_items else 0) | (L.NB_FLAG_TREE_LEAVES if tree_leaves else 0)
                    | (L.NB_FLAG_TREE_QUADRUPOLE if tree_quadrupole else 0) | (L.NB_FLAG_TREE_ENERGY if tree_energy else 0)
-                   | (L.NB_FLAG_TREE_RELATIVE if tree_alpha is not None else 0))
+                   | (L.NB_FLAG_TREE_RELATIVE if tree_alpha is not None else 0)
+                   | (L.NB_FLAG_BODY_ORDER if body_order is True else L.NB_FLAG_NO_BODY_ORDER if body_order is False else 0))
         p.sym_chunks_per_item, p.sym_aux_stream, p.sym_late_us, p.lanes_p = sym_chunks_per_item, sym_aux_stream, sym_late_us, lanes_p
         if sym_tail is not None:
             p.sym_tail[0], p.sym_tail[1], p.sym_tail[2] = sym_tail
@@ -358,6 +362,15 @@ class Simulation:
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
         L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)
+
+    def body_order(self, every: int = 0, perm: bool = False):
+        """The body order of the handle (``nb_body_order``): returns the force evaluations from one sort to the next (0: the handle
+        sweeps its bodies in the caller's order); ``every`` > 0 sets that cadence first; with ``perm`` returns ``(every, perm)``, perm
+        the uint32 permutation of the last sort (sorted position -> body index; synchronises)."""
+        out = np.empty(self.n, dtype=np.uint32) if perm else None
+        ev = C.c_uint32(0)
+        L.check("nb_body_order", self._lib.nb_body_order(self._h, every, out.ctypes.data if perm else None, C.byref(ev)), self._lib)
+        return (int(ev.value), out) if perm else int(ev.value)
 
     def dump(self, path: str) -> None:
         L.check("nb_dump", self._lib.nb_dump(self._h, str(path).encode()), self._lib)

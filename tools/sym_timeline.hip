@@ -8,7 +8,7 @@
 // workgroup end to the last one).
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Inbodysim_amd/csrc -Iinclude -o build/sym_timeline tools/sym_timeline.hip nbodysim_amd/csrc/nb_plan.cpp
-//   build/sym_timeline [n=25000] [tile=512|2048] [L=0] [masses=1: 0 equal | 1 individual | 2 individual, mass-scaled body] [pairs=0] [reps=20] [shift=0] [stagger=0]
+//   build/sym_timeline [n=25000] [tile=512|2048] [L=0] [masses=1: 0 equal | 1 individual | 2 individual, mass-scaled body] [pairs=0] [reps=20] [shift=0] [stagger=0] [delay_ticks=0] [delay_div=256] [positions.f32x2]
 //   stagger = k > 0 (experiment): among the first `stagger` items of the list every other adjacent pair of symmetric items of the same
 //   tile is MERGED into one item of twice the chunks, so that the workgroups that start together on a CU no longer end together
 // stamps INSIDE a workgroup (the body calls NB_STAMP(1) once the stationary particles are loaded, NB_STAMP(2) after the sweep of
@@ -69,6 +69,7 @@ int main(int argc, char **argv)
     const int stagger = argc > 8 ? atoi(argv[8]) : 0;
     const uint32_t delay_ticks = argc > 9 ? (uint32_t)atoi(argv[9]) : 0u;      // experiment: first-wave workgroup k of a CU starts k x this many 10-ns ticks late
     const uint32_t delay_div = argc > 10 ? (uint32_t)atoi(argv[10]) : 256u;    // ... with k = (index / delay_div) mod 4            // > 0: desynchronise the workgroups that share a CU (see below)
+    const char *posfile = argc > 11 ? argv[11] : nullptr;                      // positions from a file instead of uniform draws (the operand-order experiment)
     hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
 
@@ -94,6 +95,11 @@ int main(int argc, char **argv)
     std::uniform_real_distribution<float> U(-1.f, 1.f);
     std::vector<float2> hp(n); std::vector<float> hm(n);
     for (uint32_t i = 0; i < n; ++i) { hp[i] = make_float2(U(rng), U(rng)); hm[i] = general ? 0.5f + 0.5f * std::fabs(U(rng)) : 1.0f / n; }
+    if (posfile) {                                      // the caller's bodies, in the caller's order: n raw float2 records
+        FILE *f = fopen(posfile, "rb");
+        if (!f || fread(hp.data(), sizeof(float2), n, f) != n) { fprintf(stderr, "%s: cannot read %u float2 positions\n", posfile, n); return 1; }
+        fclose(f);
+    }
     float2 *pos, *ss, *sr; float *mass, *sigma; SymItem *items; Stamp *st;
     const size_t rows = pl.rowbase[pl.tiles];
     CK(hipMalloc(&pos, n * sizeof(float2))); CK(hipMalloc(&mass, n * sizeof(float)));
