@@ -953,14 +953,12 @@ static int launch_sym_items(nb_sim *s, uint32_t first, uint32_t count, hipStream
         const real eps2 = (real)s->p.eps * (real)s->p.eps, umv = um ? (real)s->um_mass : (real)1;
         const vec *pos = (const vec *)sym_positions(s);     // an ordered handle: the sorted copies (nb_order_host.hip.h)
         vec *ss = (vec *)s->sym_slab_s, *sr = (vec *)s->sym_slab_r;
-        // the kernels' leading arguments differ by layout: (pos), (pos, mass) or (pos, mass, sigma)
+        // the kernels' leading arguments: (pos, mass) in fp64 (3-D reads pos.w and not `mass`), (pos, mass, sigma) in fp32 2-D, (pos) in fp32 3-D
         auto go = [&](auto kernel, auto... lead) { return launch_sym_kernel(s, kernel, count, slot, st, lead..., items, ss, sr, n, eps2, umv); };
-        if constexpr (L.dims3 && std::is_same_v<real, double>)
-            return with_flags([&](auto u) { return go(force_sym3_f64<u>, pos); }, um);
+        if constexpr (std::is_same_v<real, double>)
+            return with_flags([&](auto u) { return go(force_sym_f64<decltype(L), u>, pos, (const double *)sym_masses(s)); }, um);
         else if constexpr (L.dims3)
             return with_flags([&](auto q, auto u, auto pp) { return go(force_sym3_f32<q ? RSQ_QUAKE : RSQ_EXACT, u, pp>, pos); }, quake, um, pairs);
-        else if constexpr (std::is_same_v<real, double>)
-            return with_flags([&](auto u) { return go(force_sym_f64<u>, pos, (const double *)sym_masses(s)); }, um);
         else
             return with_flags([&](auto q, auto pp, auto ws) {
                 constexpr int RQ = q ? RSQ_QUAKE : RSQ_EXACT;

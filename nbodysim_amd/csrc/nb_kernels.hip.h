@@ -18,9 +18,17 @@
 //   sym_gather / integrate          fixed-order sums of the partial slabs + kick/drift (no atomics:
 //                                   results are reproducible run to run)
 //   pack/unpack/energy/sum_partials AoS <-> SoA, diagnostics, in-process reduce-scatter
-// The one-sided force kernels, integrate, kick/drift, pack/unpack, energy and momentum are keyed on a Layout
-// (precision x 2-D / 3-D) and serve the 3-D handles too; the 3-D symmetric kernels and their gather are in
-// nb_kernels3d.hip.h.
+// The force kernels, integrate, kick/drift, pack/unpack, energy and momentum are keyed on a Layout (precision x 2-D / 3-D)
+// and serve the 3-D handles too (build extension); only the gather of the symmetric slabs has a 3-D twin
+// of its own, sym_gather3 (one particle per thread where sym_gather sums a pair).
+//
+// 3-D: the reference is strictly 2-D (`Vec2`), but each `alignas(16) Vec2 {float x, y;}` carries 8 bytes of padding right
+// after y (Nbodysim/headers/Vec2.hpp:17-20), so z fits at offset +8 of pos / vel / acc without moving x, y or changing
+// sizeof(Body) = 64 (Body.hpp:6-13).  With nb_params.dims = 3 the library reads and writes those slots and evaluates the
+// same softened force with a third component (20 algorithmic flop per pair instead of 14).  There is no reference
+// arithmetic to be bit-exact with there: parity is against the fp64 restatement only ("parity unpinned").
+// Device layout in 3-D: positions as real4 {x, y, z, m} (float4: one 16-byte load per particle; double4: two; the mass
+// rides along), velocities / accelerations / slab rows as real4 {·, ·, ·, 0}.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -607,12 +615,14 @@ enum { MM_UNIFORM = 0, MM_GENERAL = 1, MM_SCALED = 2 };
 // WS (wave split, force_sym_f32<..., WS = true>): the 4 waves of the workgroup hold the SAME stationary particles and
 // take the item's chunks in turn (wave w: chunks w, w + 4, ...), so a travelling partial is complete inside ONE wave
 // and is stored straight from the registers: no LDS combine, no barrier per chunk.
-template <int RSQ, int MM, bool DIAG, bool WS = false, bool WT = false>
+// L = Layout<float, true> is the 3-D form: z beside x and y (zi, az, zq, aqz: 3-D only), the mass from pos.w, float4 slab
+// elements; 9-10 ds_bpermute_b32 per step and 14 packed + 2 v_rsq_f32 per body.  Classic tiles, plain stores, MM_UNIFORM / MM_GENERAL.
+template <int RSQ, int MM, bool DIAG, bool WS = false, bool WT = false, typename L = Layout<float, false>>
 __device__ __forceinline__
-void sym_chunks(const float2 *__restrict__ pos, const float *__restrict__ mass, const float *__restrict__ sigma,
-                float2 *__restrict__ slab_r_row, uint32_t n, uint32_t c0, uint32_t cnt,
-                const v2f (&xi)[SYM_P], const v2f (&yi)[SYM_P], const v2f (&mi)[SYM_P],
-                v2f (&ax)[SYM_P], v2f (&ay)[SYM_P], float eps2, float um_mass, float2 (*red)[4][64])
+void sym_chunks(const typename L::vec *__restrict__ pos, const float *__restrict__ mass, const float *__restrict__ sigma,
+                typename L::vec *__restrict__ slab_r_row, uint32_t n, uint32_t c0, uint32_t cnt,
+                const v2f (&xi)[SYM_P], const v2f (&yi)[SYM_P], const v2f (&zi)[SYM_P], const v2f (&mi)[SYM_P],
+                v2f (&ax)[SYM_P], v2f (&ay)[SYM_P], v2f (&az)[SYM_P], float eps2, float um_mass, typename L::vec (*red)[4][64])
 {
     constexpr bool UM = MM == MM_UNIFORM, MS = MM == MM_SCALED;
     const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
@@ -621,34 +631,36 @@ void sym_chunks(const float2 *__restrict__ pos, const float *__restrict__ mass, 
 
     // chunk c0 into registers.  MM_SCALED: (xq, yq) hold the PRE-MULTIPLIED position sigma (x, y), mq holds -sigma and
     // eq = sigma^2 eps^2; padding lanes take sigma = 1 at PAD_XY (their g^3 underflows to 0 like everywhere else)
-    float xq = PAD_XY, yq = PAD_XY, mq = MS ? -1.0f : 0.f, eq = eps2;
-    auto fetch = [&](uint32_t j, float &x, float &y, float &m, float &e) {
-        x = PAD_XY; y = PAD_XY; m = MS ? -1.0f : 0.f; e = eps2;
+    float xq = PAD_XY, yq = PAD_XY, zq = PAD_XY, mq = MS ? -1.0f : 0.f, eq = eps2;
+    auto fetch = [&](uint32_t j, float &x, float &y, float &z, float &m, float &e) {
+        x = PAD_XY; y = PAD_XY; z = PAD_XY; m = MS ? -1.0f : 0.f; e = eps2;
         if (j < n) {
-            const float2 pj = pos[j];
+            const auto pj = pos[j];
             if constexpr (MS) { const float sg = sigma[j]; x = pj.x * sg; y = pj.y * sg; m = -sg; e = (sg * sg) * eps2; }
+            else if constexpr (L::dims3) { x = pj.x; y = pj.y; z = pj.z; m = pj.w; }
             else { x = pj.x; y = pj.y; if constexpr (!UM) m = mass[j]; }
         }
     };
     constexpr uint32_t CS = WS ? 4u : 1u;              // chunk stride of this wave
     const uint32_t cfirst = WS ? w : 0u;
-    fetch(cfirst < cnt ? (c0 + cfirst) * SYM_CH + lane : n, xq, yq, mq, eq);
+    fetch(cfirst < cnt ? (c0 + cfirst) * SYM_CH + lane : n, xq, yq, zq, mq, eq);
     for (uint32_t c = cfirst; c < cnt; c += CS) {
         // next chunk in flight behind the 64 steps
-        float xn, yn, mn, en;
-        fetch(c + CS < cnt ? (c0 + c + CS) * SYM_CH + lane : n, xn, yn, mn, en);
-        v2f aqx = {0.f, 0.f}, aqy = {0.f, 0.f};
+        float xn, yn, zn, mn, en;
+        fetch(c + CS < cnt ? (c0 + c + CS) * SYM_CH + lane : n, xn, yn, zn, mn, en);
+        v2f aqx = {0.f, 0.f}, aqy = {0.f, 0.f}, aqz = {0.f, 0.f};
 #pragma unroll SYM_UNROLL
         for (int step = 0; step < 64; ++step) {
             // positions of the next step do not depend on this step's arithmetic: rotate them early
             const float xr = lane_rot(xq, addr), yr = lane_rot(yq, addr);
-            float mr = 0.f, er = 0.f;
+            float zr = 0.f, mr = 0.f, er = 0.f;
+            if constexpr (L::dims3) zr = lane_rot(zq, addr);
             if constexpr (!UM) mr = lane_rot(mq, addr);
             if constexpr (MS) er = lane_rot(eq, addr);
-            const v2f xj = {xq, xq}, yj = {yq, yq};
+            const v2f xj = {xq, xq}, yj = {yq, yq}, zj = {zq, zq};
 #pragma unroll
             for (int p = 0; p < SYM_P; ++p) {
-                v2f dx, dy, r2;
+                v2f dx, dy, dz, r2;
                 if constexpr (MS) {
                     const v2f ns = {mq, mq};                               // -sigma_j
                     dx = __builtin_elementwise_fma(ns, xi[p], xj);         // sigma_j (x_j - x_i)
@@ -657,9 +669,11 @@ void sym_chunks(const float2 *__restrict__ pos, const float *__restrict__ mass, 
                 } else {
                     dx = xj - xi[p];
                     dy = yj - yi[p];
+                    if constexpr (L::dims3) dz = zj - zi[p];
                     r2 = __builtin_elementwise_fma(dx, dx, e2);
                 }
                 r2 = __builtin_elementwise_fma(dy, dy, r2);
+                if constexpr (L::dims3) r2 = __builtin_elementwise_fma(dz, dz, r2);
                 v2f inv;
                 if constexpr (RSQ == RSQ_EXACT) inv = (v2f){__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
                 else inv = quake_rsqrt2(r2);
@@ -667,6 +681,7 @@ void sym_chunks(const float2 *__restrict__ pos, const float *__restrict__ mass, 
                 if constexpr (UM || MS) {
                     ax[p] = __builtin_elementwise_fma(inv3, dx, ax[p]);
                     ay[p] = __builtin_elementwise_fma(inv3, dy, ay[p]);
+                    if constexpr (L::dims3) az[p] = __builtin_elementwise_fma(inv3, dz, az[p]);
                     if constexpr (!DIAG) {
                         if constexpr (MS) {
                             const v2f sj = mi[p] * inv3;                   // m_i g^3: the m_j it still carries is divided out per chunk
@@ -675,50 +690,58 @@ void sym_chunks(const float2 *__restrict__ pos, const float *__restrict__ mass, 
                         } else {
                             aqx = __builtin_elementwise_fma(-inv3, dx, aqx);
                             aqy = __builtin_elementwise_fma(-inv3, dy, aqy);
+                            if constexpr (L::dims3) aqz = __builtin_elementwise_fma(-inv3, dz, aqz);
                         }
                     }
                 } else {
                     const v2f si = (v2f){mq, mq} * inv3;       // force ON the stationary pair: m_j / r^3
                     ax[p] = __builtin_elementwise_fma(si, dx, ax[p]);
                     ay[p] = __builtin_elementwise_fma(si, dy, ay[p]);
+                    if constexpr (L::dims3) az[p] = __builtin_elementwise_fma(si, dz, az[p]);
                     if constexpr (!DIAG) {
                         const v2f sj = mi[p] * inv3;           // force ON the travelling particle: m_i / r^3
                         aqx = __builtin_elementwise_fma(-sj, dx, aqx);
                         aqy = __builtin_elementwise_fma(-sj, dy, aqy);
+                        if constexpr (L::dims3) aqz = __builtin_elementwise_fma(-sj, dz, aqz);
                     }
                 }
             }
             xq = xr; yq = yr;
+            if constexpr (L::dims3) zq = zr;
             if constexpr (!UM) mq = mr;
             if constexpr (MS) eq = er;
             if constexpr (!DIAG) {
                 aqx.x = lane_rot(aqx.x, addr); aqx.y = lane_rot(aqx.y, addr);
                 aqy.x = lane_rot(aqy.x, addr); aqy.y = lane_rot(aqy.y, addr);
+                if constexpr (L::dims3) { aqz.x = lane_rot(aqz.x, addr); aqz.y = lane_rot(aqz.y, addr); }
             }
         }
         if constexpr (!DIAG) {
             // after 64 rotations lane l holds the accumulator of travelling particle (chunk, l):
             // combine the 4 waves (4 different stationary sets) in wave order and store once.
-            float2 r = make_float2(aqx.x + aqx.y, aqy.x + aqy.y);
-            if constexpr (UM) { r.x *= um_mass; r.y *= um_mass; }
+            typename L::vec r;
+            if constexpr (L::dims3) r = make_float4(aqx.x + aqx.y, aqy.x + aqy.y, aqz.x + aqz.y, 0.f);
+            else r = make_float2(aqx.x + aqx.y, aqy.x + aqy.y);
+            if constexpr (UM) { r.x *= um_mass; r.y *= um_mass; if constexpr (L::dims3) r.z *= um_mass; }
             if constexpr (MS) { const float s2 = mq * mq; r.x *= s2; r.y *= s2; }      // / m_j: the particle is back in its home lane
             if constexpr (WS) {
                 const uint32_t j = (c0 + c) * SYM_CH + lane;      // this wave alone met the chunk: its sum is the partial
                 if (j < n) store8<WT>(&slab_r_row[j], r);
             } else {
-                float2 (*rb)[64] = red[c & 1u];
+                typename L::vec (*rb)[64] = red[c & 1u];
                 rb[w][lane] = r;
                 __syncthreads();
                 if (w == 0) {
                     const uint32_t j = (c0 + c) * SYM_CH + lane;
-                    float2 a = rb[0][lane];
+                    typename L::vec a = rb[0][lane];
 #pragma unroll
-                    for (int k = 1; k < 4; ++k) { a.x += rb[k][lane].x; a.y += rb[k][lane].y; }
-                    if (j < n) store8<WT>(&slab_r_row[j], a);
+                    for (int k = 1; k < 4; ++k) { a.x += rb[k][lane].x; a.y += rb[k][lane].y; if constexpr (L::dims3) a.z += rb[k][lane].z; }
+                    if (j < n) { if constexpr (L::dims3) slab_r_row[j] = a; else store8<WT>(&slab_r_row[j], a); }
                 }
             }
         }
         xq = xn; yq = yn;
+        if constexpr (L::dims3) zq = zn;
         if constexpr (!UM) mq = mn;
         if constexpr (MS) eq = en;
     }
@@ -735,45 +758,53 @@ void sym_chunks(const float2 *__restrict__ pos, const float *__restrict__ mass, 
 // The stationary accumulators become per-particle pairs {from q0, from q1} (32 registers instead of 16), summed at the
 // end.  An odd chunk count leaves the second half of the last pair empty (PAD particles: half of that pair's work is
 // wasted), so the planner cuts items into even chunk counts for handles that run this kernel (SymTuning::even_chunks).
-template <int RSQ, int MM, bool DIAG, bool WS = false, bool WT = false>
+// L = Layout<float, true>: the 3-D form, as in sym_chunks (12 ds_bpermute_b32 per 16 pairs instead of 9 per 8).
+template <int RSQ, int MM, bool DIAG, bool WS = false, bool WT = false, typename L = Layout<float, false>>
 __device__ __forceinline__
-void sym_chunks2(const float2 *__restrict__ pos, const float *__restrict__ mass,
-                 float2 *__restrict__ slab_r_row, uint32_t n, uint32_t c0, uint32_t cnt,
-                 const v2f (&xi)[SYM_P], const v2f (&yi)[SYM_P], const v2f (&mi)[SYM_P],
-                 v2f (&ax)[SYM_P], v2f (&ay)[SYM_P], float eps2, float um_mass, float4 (*red)[4][64])
+void sym_chunks2(const typename L::vec *__restrict__ pos, const float *__restrict__ mass,
+                 typename L::vec *__restrict__ slab_r_row, uint32_t n, uint32_t c0, uint32_t cnt,
+                 const v2f (&xi)[SYM_P], const v2f (&yi)[SYM_P], const v2f (&zi)[SYM_P], const v2f (&mi)[SYM_P],
+                 v2f (&ax)[SYM_P], v2f (&ay)[SYM_P], v2f (&az)[SYM_P], float eps2, float um_mass, float4 (*red)[4][64])
 {
     static_assert(MM != MM_SCALED, "the mass-scaled body keeps the one-chunk form");
     constexpr bool UM = MM == MM_UNIFORM;
     const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
     const int addr = (int)(((lane + 1u) & 63u) * 4u);
     const v2f e2 = {eps2, eps2};
-    v2f bx[2 * SYM_P], by[2 * SYM_P];                  // stationary particle s = 2p + h: {partial from q0, partial from q1}
+    v2f bx[2 * SYM_P], by[2 * SYM_P], bz[2 * SYM_P];   // stationary particle s = 2p + h: {partial from q0, partial from q1}
 #pragma unroll
-    for (int k = 0; k < 2 * SYM_P; ++k) { bx[k] = (v2f){0.f, 0.f}; by[k] = (v2f){0.f, 0.f}; }
+    for (int k = 0; k < 2 * SYM_P; ++k) { bx[k] = (v2f){0.f, 0.f}; by[k] = (v2f){0.f, 0.f}; bz[k] = (v2f){0.f, 0.f}; }
 
-    auto fetch = [&](uint32_t c, v2f &x, v2f &y, v2f &m) {          // chunks c and c + 1 of the item (if inside it)
+    auto fetch = [&](uint32_t c, v2f &x, v2f &y, v2f &m) {          // chunks c and c + 1 of the item (if inside it); returns their z (3-D)
         x = (v2f){PAD_XY, PAD_XY}; y = x; m = (v2f){0.f, 0.f};
+        v2f z = x;
         if (c < cnt) {
             const uint32_t j = (c0 + c) * SYM_CH + lane;
-            if (j < n) { const float2 pj = pos[j]; x.x = pj.x; y.x = pj.y; if constexpr (!UM) m.x = mass[j]; }
+            if (j < n) {
+                const auto pj = pos[j]; x.x = pj.x; y.x = pj.y;
+                if constexpr (L::dims3) { z.x = pj.z; m.x = pj.w; } else if constexpr (!UM) m.x = mass[j];
+            }
         }
         if (c + 1 < cnt) {
             const uint32_t j = (c0 + c + 1) * SYM_CH + lane;
-            if (j < n) { const float2 pj = pos[j]; x.y = pj.x; y.y = pj.y; if constexpr (!UM) m.y = mass[j]; }
+            if (j < n) {
+                const auto pj = pos[j]; x.y = pj.x; y.y = pj.y;
+                if constexpr (L::dims3) { z.y = pj.z; m.y = pj.w; } else if constexpr (!UM) m.y = mass[j];
+            }
         }
+        return z;
     };
     constexpr uint32_t CS = WS ? 8u : 2u;              // WS: wave w sweeps the chunk pairs 2w, 2w + 8, ...
-    v2f xq, yq, mq;
-    fetch(WS ? 2u * w : 0u, xq, yq, mq);
+    v2f xq, yq, mq, zq = fetch(WS ? 2u * w : 0u, xq, yq, mq);
     for (uint32_t c = WS ? 2u * w : 0u; c < cnt; c += CS) {
-        v2f xn, yn, mn;
-        fetch(c + CS, xn, yn, mn);                     // next pair in flight behind the 64 steps
-        v2f aqx = {0.f, 0.f}, aqy = {0.f, 0.f};         // {q0, q1}
+        v2f xn, yn, mn, zn = fetch(c + CS, xn, yn, mn); // next pair in flight behind the 64 steps
+        v2f aqx = {0.f, 0.f}, aqy = {0.f, 0.f}, aqz = {0.f, 0.f};   // {q0, q1}
 #pragma unroll SYM_UNROLL2
         for (int step = 0; step < 64; ++step) {
             const v2f xr = {lane_rot(xq.x, addr), lane_rot(xq.y, addr)};
             const v2f yr = {lane_rot(yq.x, addr), lane_rot(yq.y, addr)};
-            v2f mr = {0.f, 0.f};
+            v2f zr = {0.f, 0.f}, mr = {0.f, 0.f};
+            if constexpr (L::dims3) zr = (v2f){lane_rot(zq.x, addr), lane_rot(zq.y, addr)};
             if constexpr (!UM) mr = (v2f){lane_rot(mq.x, addr), lane_rot(mq.y, addr)};
 #pragma unroll
             for (int p = 0; p < SYM_P; ++p) {
@@ -782,8 +813,11 @@ void sym_chunks2(const float2 *__restrict__ pos, const float *__restrict__ mass,
                     const float xs = h ? xi[p].y : xi[p].x, ys = h ? yi[p].y : yi[p].x;
                     const v2f dx = xq - (v2f){xs, xs};
                     const v2f dy = yq - (v2f){ys, ys};
+                    v2f dz;
+                    if constexpr (L::dims3) { const float zs = h ? zi[p].y : zi[p].x; dz = zq - (v2f){zs, zs}; }
                     v2f r2 = __builtin_elementwise_fma(dx, dx, e2);
                     r2 = __builtin_elementwise_fma(dy, dy, r2);
+                    if constexpr (L::dims3) r2 = __builtin_elementwise_fma(dz, dz, r2);
                     v2f inv;
                     if constexpr (RSQ == RSQ_EXACT) inv = (v2f){__builtin_amdgcn_rsqf(r2.x), __builtin_amdgcn_rsqf(r2.y)};
                     else inv = quake_rsqrt2(r2);
@@ -791,31 +825,52 @@ void sym_chunks2(const float2 *__restrict__ pos, const float *__restrict__ mass,
                     if constexpr (UM) {
                         bx[2 * p + h] = __builtin_elementwise_fma(inv3, dx, bx[2 * p + h]);
                         by[2 * p + h] = __builtin_elementwise_fma(inv3, dy, by[2 * p + h]);
+                        if constexpr (L::dims3) bz[2 * p + h] = __builtin_elementwise_fma(inv3, dz, bz[2 * p + h]);
                         if constexpr (!DIAG) {
                             aqx = __builtin_elementwise_fma(-inv3, dx, aqx);
                             aqy = __builtin_elementwise_fma(-inv3, dy, aqy);
+                            if constexpr (L::dims3) aqz = __builtin_elementwise_fma(-inv3, dz, aqz);
                         }
                     } else {
                         const v2f si = mq * inv3;                          // force ON the stationary particle: m_q / r^3 per half
                         bx[2 * p + h] = __builtin_elementwise_fma(si, dx, bx[2 * p + h]);
                         by[2 * p + h] = __builtin_elementwise_fma(si, dy, by[2 * p + h]);
+                        if constexpr (L::dims3) bz[2 * p + h] = __builtin_elementwise_fma(si, dz, bz[2 * p + h]);
                         if constexpr (!DIAG) {
                             const float ms = h ? mi[p].y : mi[p].x;
                             const v2f sj = (v2f){ms, ms} * inv3;           // force ON the travelling pair: m_s / r^3
                             aqx = __builtin_elementwise_fma(-sj, dx, aqx);
                             aqy = __builtin_elementwise_fma(-sj, dy, aqy);
+                            if constexpr (L::dims3) aqz = __builtin_elementwise_fma(-sj, dz, aqz);
                         }
                     }
                 }
             }
             xq = xr; yq = yr;
+            if constexpr (L::dims3) zq = zr;
             if constexpr (!UM) mq = mr;
             if constexpr (!DIAG) {
                 aqx = (v2f){lane_rot(aqx.x, addr), lane_rot(aqx.y, addr)};
                 aqy = (v2f){lane_rot(aqy.x, addr), lane_rot(aqy.y, addr)};
+                if constexpr (L::dims3) aqz = (v2f){lane_rot(aqz.x, addr), lane_rot(aqz.y, addr)};
             }
         }
-        if constexpr (!DIAG) {
+        if constexpr (!DIAG && L::dims3) {
+            // the same combine with one float4 per travelling particle: [half q0 | half q1][4 waves][64 lanes], double buffered
+            float4 r0 = make_float4(aqx.x, aqy.x, aqz.x, 0.f), r1 = make_float4(aqx.y, aqy.y, aqz.y, 0.f);
+            if constexpr (UM) { r0.x *= um_mass; r0.y *= um_mass; r0.z *= um_mass; r1.x *= um_mass; r1.y *= um_mass; r1.z *= um_mass; }
+            float4 (*rb)[4][64] = red + 2u * ((c >> 1) & 1u);
+            rb[0][w][lane] = r0;
+            rb[1][w][lane] = r1;
+            __syncthreads();
+            if (w < 2 && c + w < cnt) {                                // wave 0 stores chunk c, wave 1 chunk c + 1
+                const uint32_t j = (c0 + c + w) * SYM_CH + lane;
+                float4 a = rb[w][0][lane];
+#pragma unroll
+                for (int k = 1; k < 4; ++k) { a.x += rb[w][k][lane].x; a.y += rb[w][k][lane].y; a.z += rb[w][k][lane].z; }
+                if (j < n) slab_r_row[j] = a;
+            }
+        } else if constexpr (!DIAG) {
             // lane l holds the accumulators of travelling particles (chunk c, l) and (chunk c + 1, l): combine the 4 waves
             // in wave order; wave 0 stores chunk c, wave 1 chunk c + 1
             float4 r = make_float4(aqx.x, aqy.x, aqx.y, aqy.y);
@@ -841,12 +896,14 @@ void sym_chunks2(const float2 *__restrict__ pos, const float *__restrict__ mass,
             }
         }
         xq = xn; yq = yn;
+        if constexpr (L::dims3) zq = zn;
         if constexpr (!UM) mq = mn;
     }
 #pragma unroll
     for (int p = 0; p < SYM_P; ++p) {
         ax[p] += (v2f){bx[2 * p].x + bx[2 * p].y, bx[2 * p + 1].x + bx[2 * p + 1].y};
         ay[p] += (v2f){by[2 * p].x + by[2 * p].y, by[2 * p + 1].x + by[2 * p + 1].y};
+        if constexpr (L::dims3) az[p] += (v2f){bz[2 * p].x + bz[2 * p].y, bz[2 * p + 1].x + bz[2 * p + 1].y};
     }
 }
 
@@ -859,51 +916,70 @@ void sym_chunks2(const float2 *__restrict__ pos, const float *__restrict__ mass,
 #ifndef NB_STAMP
 #define NB_STAMP(k)          // measurement hook of tools/sym_timeline.hip (stamps inside a workgroup); nothing in the library
 #endif
-template <int RSQ, int MM, bool PAIRS = false, bool WS = false, bool WT = false>
+// L = Layout<float, true> (3-D, see sym_chunks): classic tiles, plain slab stores, MM_UNIFORM / MM_GENERAL only; `mass` and
+// `sigma` are not read (force_sym3_f32 passes none).
+template <int RSQ, int MM, bool PAIRS = false, bool WS = false, bool WT = false, typename L = Layout<float, false>>
 __device__ __forceinline__
-void force_sym_f32_body(const float2 *__restrict__ pos, const float *__restrict__ mass, const float *__restrict__ sigma,
+void force_sym_f32_body(const typename L::vec *__restrict__ pos, const float *__restrict__ mass, const float *__restrict__ sigma,
                         const SymItem it,
-                        float2 *__restrict__ slab_s, float2 *__restrict__ slab_r,
+                        typename L::vec *__restrict__ slab_s, typename L::vec *__restrict__ slab_r,
                         uint32_t n, float eps2, float um_mass)
 {
     constexpr bool UM = MM == MM_UNIFORM;
     constexpr uint32_t SB = WS ? SYM_SB_WS : SYM_SB;
     static_assert(!(PAIRS && MM == MM_SCALED), "the mass-scaled body keeps the one-chunk form");
     static_assert(SYM_WT == SYM_SB_WS && (!WS || SYM_P == 4), "a wave-split tile is one wave's stationary set; wave w finishes register pair w");
-    __shared__ float4 red4[WS ? 4 * SYM_P : 2 * 4][64];          // classic: [2][4][64] chunk combine; WS: [4 waves][SYM_P][64] final sums
-    float2 (*red)[4][64] = reinterpret_cast<float2 (*)[4][64]>(red4);
+    static_assert(!L::dims3 || (!WS && !WT && MM != MM_SCALED), "3-D: classic tiles, plain stores, no mass scaling");
+    // classic: [2][4][64] chunk combine; WS: [4 waves][SYM_P][64] final sums; 3-D: float4 [PAIRS ? 4 : 2][4][64] chunk combine
+    __shared__ float4 red4[L::dims3 ? (PAIRS ? 4 : 2) * 4 : WS ? 4 * SYM_P : 2 * 4][64];
+    typename L::vec (*red)[4][64] = reinterpret_cast<typename L::vec (*)[4][64]>(red4);
     float4 (*red2)[4][64] = reinterpret_cast<float4 (*)[4][64]>(red4);
     const bool diag = it.diag != 0;
     const uint32_t s_row = it.s_row;
     const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
 
-    v2f xi[SYM_P], yi[SYM_P], mi[SYM_P], ax[SYM_P], ay[SYM_P];
+    v2f xi[SYM_P], yi[SYM_P], zi[SYM_P], mi[SYM_P], ax[SYM_P], ay[SYM_P], az[SYM_P];      // zi, az: 3-D only
     uint32_t li[SYM_P];
 #pragma unroll
     for (int p = 0; p < SYM_P; ++p) {
         li[p] = (WS ? 0u : w * SYM_WT) + (uint32_t)p * 128u + 2u * lane;      // index inside the block-tile
         const uint32_t g0 = it.tile * SB + li[p], g1 = g0 + 1;
         // particles past the end sit at PAD_XY with mass 0: they neither feel nor exert force
-        float2 p0 = make_float2(PAD_XY, PAD_XY), p1 = p0;
-        float m0 = 0.f, m1 = 0.f;
-        if (g0 < n) { p0 = pos[g0]; if constexpr (!UM) m0 = mass[g0]; }
-        if (g1 < n) { p1 = pos[g1]; if constexpr (!UM) m1 = mass[g1]; }
-        xi[p] = (v2f){p0.x, p1.x}; yi[p] = (v2f){p0.y, p1.y}; mi[p] = (v2f){m0, m1};
+        if constexpr (L::dims3) {
+            float4 p0 = make_float4(PAD_XY, PAD_XY, PAD_XY, 0.f), p1 = p0;
+            if (g0 < n) p0 = pos[g0];
+            if (g1 < n) p1 = pos[g1];
+            xi[p] = (v2f){p0.x, p1.x}; yi[p] = (v2f){p0.y, p1.y}; zi[p] = (v2f){p0.z, p1.z}; mi[p] = (v2f){p0.w, p1.w};
+            az[p] = (v2f){0.f, 0.f};
+        } else {
+            float2 p0 = make_float2(PAD_XY, PAD_XY), p1 = p0;
+            float m0 = 0.f, m1 = 0.f;
+            if (g0 < n) { p0 = pos[g0]; if constexpr (!UM) m0 = mass[g0]; }
+            if (g1 < n) { p1 = pos[g1]; if constexpr (!UM) m1 = mass[g1]; }
+            xi[p] = (v2f){p0.x, p1.x}; yi[p] = (v2f){p0.y, p1.y}; mi[p] = (v2f){m0, m1};
+        }
         ax[p] = (v2f){0.f, 0.f}; ay[p] = (v2f){0.f, 0.f};
     }
     NB_STAMP(1);                                                  // (tools/sym_timeline.hip only; empty in the product)
-    float2 *__restrict__ rrow = slab_r + it.r_base;               // rrow[j] = travelling partial of particle j
+    typename L::vec *__restrict__ rrow = slab_r + it.r_base;      // rrow[j] = travelling partial of particle j
     if constexpr (PAIRS) {
-        if (diag) sym_chunks2<RSQ, MM, true, WS, WT>(pos, mass, rrow, n, it.c0, it.cnt, xi, yi, mi, ax, ay, eps2, um_mass, red2);
-        else      sym_chunks2<RSQ, MM, false, WS, WT>(pos, mass, rrow, n, it.c0, it.cnt, xi, yi, mi, ax, ay, eps2, um_mass, red2);
+        if (diag) sym_chunks2<RSQ, MM, true, WS, WT, L>(pos, mass, rrow, n, it.c0, it.cnt, xi, yi, zi, mi, ax, ay, az, eps2, um_mass, red2);
+        else      sym_chunks2<RSQ, MM, false, WS, WT, L>(pos, mass, rrow, n, it.c0, it.cnt, xi, yi, zi, mi, ax, ay, az, eps2, um_mass, red2);
     } else {
-        if (diag) sym_chunks<RSQ, MM, true, WS, WT>(pos, mass, sigma, rrow, n, it.c0, it.cnt, xi, yi, mi, ax, ay, eps2, um_mass, red);
-        else      sym_chunks<RSQ, MM, false, WS, WT>(pos, mass, sigma, rrow, n, it.c0, it.cnt, xi, yi, mi, ax, ay, eps2, um_mass, red);
+        if (diag) sym_chunks<RSQ, MM, true, WS, WT, L>(pos, mass, sigma, rrow, n, it.c0, it.cnt, xi, yi, zi, mi, ax, ay, az, eps2, um_mass, red);
+        else      sym_chunks<RSQ, MM, false, WS, WT, L>(pos, mass, sigma, rrow, n, it.c0, it.cnt, xi, yi, zi, mi, ax, ay, az, eps2, um_mass, red);
     }
 
     NB_STAMP(2);
-    float2 *__restrict__ out = slab_s + (size_t)s_row * SB;
-    if constexpr (WS) {
+    typename L::vec *__restrict__ out = slab_s + (size_t)s_row * SB;
+    if constexpr (L::dims3) {
+#pragma unroll
+        for (int p = 0; p < SYM_P; ++p) {
+            if constexpr (UM) { ax[p] *= um_mass; ay[p] *= um_mass; az[p] *= um_mass; }
+            out[li[p]] = make_float4(ax[p].x, ay[p].x, az[p].x, 0.f);
+            out[li[p] + 1] = make_float4(ax[p].y, ay[p].y, az[p].y, 0.f);
+        }
+    } else if constexpr (WS) {
         // the 4 waves hold partial sums of the SAME 512 particles (each over its own chunks): add them in wave order;
         // wave w finishes register pair p = w of every lane and stores its 128 particles (1 KiB)
 #pragma unroll
@@ -955,6 +1031,21 @@ void force_sym_f32(const float2 *__restrict__ pos, const float *__restrict__ mas
 #endif                       // keeping them dirty in this XCD's L2 until the kernel's end flushes them: -1.8 % step time at N = 25 000,
                              // -0.7 % at 65 536, neutral at 262 144, same bits (profiles/history/r04_write_through_ab.log)
     force_sym_f32_body<RSQ, MM, PAIRS, WS, NB_SYM_WT>(pos, mass, sigma, items[sym_item_index(ticket, first_wave, ticket_base)], slab_s, slab_r, n, eps2, um_mass);
+}
+
+// The 3-D entry of the same body (Layout<float, true>: no mass array, no sigma).  An entry of its own and not a Layout parameter
+// of force_sym_f32: a profiler prints every template argument of a kernel, defaulted ones too, and bench.py finds the 2-D kernel's
+// counter rows by that text, `nbk::force_sym_f32<RSQ, MM, PAIRS, WS>`.
+// The one-chunk sweep with equal masses is held at 5 waves per SIMD (84 VGPRs): left alone, the scheduler lands on either side of
+// that edge (84 or 100 VGPRs, 5 or 4 waves) with the order of statements that do not reach the listing.  1 = no constraint.
+template <int RSQ, bool UM, bool PAIRS = false>
+__global__ __launch_bounds__(BLOCK, UM && !PAIRS ? 5 : 1)
+void force_sym3_f32(const float4 *__restrict__ pos, const SymItem *__restrict__ items,
+                    float4 *__restrict__ slab_s, float4 *__restrict__ slab_r, uint32_t n, float eps2, float um_mass,
+                    uint32_t *ticket, uint32_t first_wave, uint32_t ticket_base)
+{
+    force_sym_f32_body<RSQ, UM ? MM_UNIFORM : MM_GENERAL, PAIRS, false, false, Layout<float, true>>(
+        pos, nullptr, nullptr, items[sym_item_index(ticket, first_wave, ticket_base)], slab_s, slab_r, n, eps2, um_mass);
 }
 
 // sigma[i] = m_i^(-1/2) for the mass-scaled kernels (correctly rounded sqrt and divide)
@@ -1114,13 +1205,75 @@ void sym_gather(const typename vec2_of<real>::type *__restrict__ slab_s,
                                       dt_kick, dt_drift, extras, flags, sb_shift, perm);
 }
 
+// sym_gather3 — the 3-D twin of sym_gather: sum of the stationary rows of particle k's tile +
+// the entries of its tile's coverage list, over particles [k0, k0 + kn); FUSE applies kick and drift (adding
+// `base`, the reduce-scattered sum of a sharded rank, when given), otherwise the sum is stored to acc_sum[k].
+template <typename real, bool FUSE>
+__global__ __launch_bounds__(BLOCK)
+void sym_gather3(const typename vec4_of<real>::type *__restrict__ slab_s, const typename vec4_of<real>::type *__restrict__ slab_r,
+                 const uint32_t *__restrict__ row_lo, const uint32_t *__restrict__ row_hi,
+                 const uint32_t *__restrict__ cov_begin, const SymCov *__restrict__ cov, uint32_t n, uint32_t k0, uint32_t kn,
+                 typename vec4_of<real>::type *__restrict__ acc_sum, const typename vec4_of<real>::type *__restrict__ base,
+                 const typename vec4_of<real>::type *__restrict__ pos_cur, typename vec4_of<real>::type *__restrict__ pos_next,
+                 typename vec4_of<real>::type *__restrict__ vel, typename vec4_of<real>::type *__restrict__ acc,
+                 real dt_kick, real dt_drift, int flags)
+{
+    typedef typename vec4_of<real>::type real4;
+    __shared__ real4 part[GATHER_Q][GATHER_T];      // one particle per thread here: the elements are 16 / 32 bytes already
+    const uint32_t p = threadIdx.x % GATHER_T, q = threadIdx.x / GATHER_T;
+    const uint32_t li = blockIdx.x * GATHER_T + p, k = k0 + li;
+    real4 a = make_real4<real>(0, 0, 0, 0);
+    if (li < kn) {
+        const uint32_t g = k / SYM_SB, loc = k % SYM_SB;
+        const uint32_t r1 = row_hi[g];
+#pragma unroll 4      // four independent loads in flight per thread; the adds keep their order
+        for (uint32_t r = row_lo[g] + q; r < r1; r += GATHER_Q) {
+            const real4 b = slab_s[(size_t)r * SYM_SB + loc];
+            a.x += b.x; a.y += b.y; a.z += b.z;
+        }
+        // coverage entries four at a time, as in sym_gather_block: descriptors, then the partials they point at,
+        // as independent batches; an entry that does not cover k reads element 0 of the slab and adds nothing; same order of adds
+        const uint32_t c1 = cov_begin[g + 1];
+        for (uint32_t i = cov_begin[g] + q; i < c1; i += 4u * GATHER_Q) {
+            SymCov cv[4];
+            bool in[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t idx = i + (uint32_t)u * GATHER_Q;
+                in[u] = idx < c1;
+                cv[u] = cov[in[u] ? idx : c1 - 1u];
+            }
+            real4 b[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                in[u] = in[u] && k >= cv[u].lo && k < cv[u].hi;
+                b[u] = slab_r[in[u] ? cv[u].base + (int64_t)k : (int64_t)0];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (in[u]) { a.x += b[u].x; a.y += b[u].y; a.z += b[u].z; }
+        }
+    }
+    part[q][p] = a;
+    __syncthreads();
+    if (q == 0 && li < kn) {
+        real4 s = part[0][p];
+#pragma unroll
+        for (int j = 1; j < GATHER_Q; ++j) { s.x += part[j][p].x; s.y += part[j][p].y; s.z += part[j][p].z; }
+        if (base) { const real4 b = base[li]; s.x += b.x; s.y += b.y; s.z += b.z; }
+        if constexpr (FUSE) kick_drift_one<Layout<real, true>, false>(s, li, pos_cur, pos_next, vel, acc, k0, dt_kick, dt_drift, 0, flags);
+        else { s.w = 0; acc_sum[k] = s; }
+    }
+}
+
 // ---------------------------------------------------------------------------
-// force_sym_f64 — the symmetric scheme in double precision (BASELINE config 5).
+// force_sym_f64 — the symmetric scheme in double precision (BASELINE config 5), 2-D and 3-D (L = Layout<double, D3>).
 // Same items, tiles (2048 particles per workgroup) and slabs as force_sym_f32; a lane holds
 // 8 stationary particles as scalars (no packed fp64 exists), the travelling particle and its
-// accumulator are rotated as pairs of 32-bit halves (10 ds_bpermute_b32 per step, 8 with UM).
+// accumulator are rotated as pairs of 32-bit halves (10 ds_bpermute_b32 per step, 8 with UM; 3-D: 14, 12).
 // Body, both directions: 2 add + 2 fma + v_rsq_f64 + 6 ops (1/r^3 with its correction, rsqrt3_f64) + 4 fma
-// (+2 mul with individual masses) for 128 ordered interactions per wave.
+// (+2 mul with individual masses) for 128 ordered interactions per wave; 3-D: 3 add + 3 fma + ... + 6 fma.
+// `mass` is the 2-D mass array (read under !UM); 3-D takes the mass from pos.w.  zi, az, zq, aqz: 3-D only.
 // ---------------------------------------------------------------------------
 constexpr int SYM_P64 = 8;    // stationary particles per lane: 64 * 8 = SYM_WT per wave
 __device__ __forceinline__ double vgpr_const(double k);
@@ -1137,104 +1290,132 @@ __device__ __forceinline__ double lane_rot64(double v, int addr)
 
 constexpr double PAD_XY64 = 1.0e150;   // r^2 = 2e300 finite, (1/r)^3 = 3.5e-451 underflows to 0
 
-template <bool UM, bool DIAG>
+template <typename L, bool UM, bool DIAG>
 __device__ __forceinline__
-void sym_chunks_f64(const double2 *__restrict__ pos, const double *__restrict__ mass,
-                    double2 *__restrict__ slab_r_row, uint32_t n, uint32_t c0, uint32_t cnt,
-                    const double (&xi)[SYM_P64], const double (&yi)[SYM_P64], const double (&mi)[SYM_P64],
-                    double (&ax)[SYM_P64], double (&ay)[SYM_P64], double eps2, double um_mass, double2 (*red)[4][64])
+void sym_chunks_f64(const typename L::vec *__restrict__ pos, const double *__restrict__ mass,
+                    typename L::vec *__restrict__ slab_r_row, uint32_t n, uint32_t c0, uint32_t cnt,
+                    const double (&xi)[SYM_P64], const double (&yi)[SYM_P64], const double (&zi)[SYM_P64], const double (&mi)[SYM_P64],
+                    double (&ax)[SYM_P64], double (&ay)[SYM_P64], double (&az)[SYM_P64], double eps2, double um_mass,
+                    typename L::vec (*red)[4][64])
 {
     const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
     const int addr = (int)(((lane + 1u) & 63u) * 4u);
     const double k15 = vgpr_const(1.5), k1875 = vgpr_const(1.875);
-    double xq = PAD_XY64, yq = PAD_XY64, mq = 0.0;
+    double xq = PAD_XY64, yq = PAD_XY64, zq = PAD_XY64, mq = 0.0;
     {
         const uint32_t j = c0 * SYM_CH + lane;
-        if (j < n) { const double2 pj = pos[j]; xq = pj.x; yq = pj.y; if constexpr (!UM) mq = mass[j]; }
+        if (j < n) {
+            const auto pj = pos[j]; xq = pj.x; yq = pj.y;
+            if constexpr (L::dims3) { zq = pj.z; mq = pj.w; } else if constexpr (!UM) mq = mass[j];
+        }
     }
     for (uint32_t c = 0; c < cnt; ++c) {
-        double xn = PAD_XY64, yn = PAD_XY64, mn = 0.0;
+        double xn = PAD_XY64, yn = PAD_XY64, zn = PAD_XY64, mn = 0.0;
         {
             const uint32_t j = (c0 + c + 1) * SYM_CH + lane;
-            if (c + 1 < cnt && j < n) { const double2 pj = pos[j]; xn = pj.x; yn = pj.y; if constexpr (!UM) mn = mass[j]; }
+            if (c + 1 < cnt && j < n) {
+                const auto pj = pos[j]; xn = pj.x; yn = pj.y;
+                if constexpr (L::dims3) { zn = pj.z; mn = pj.w; } else if constexpr (!UM) mn = mass[j];
+            }
         }
-        double aqx = 0.0, aqy = 0.0;
+        double aqx = 0.0, aqy = 0.0, aqz = 0.0;
         for (int step = 0; step < 64; ++step) {
             const double xr = lane_rot64(xq, addr), yr = lane_rot64(yq, addr);
-            double mr = 0.0;
+            double zr = 0.0, mr = 0.0;
+            if constexpr (L::dims3) zr = lane_rot64(zq, addr);
             if constexpr (!UM) mr = lane_rot64(mq, addr);
 #pragma unroll
             for (int p = 0; p < SYM_P64; ++p) {
                 const double dx = xq - xi[p], dy = yq - yi[p];
-                const double r2 = __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2));
+                double dz = 0.0;
+                if constexpr (L::dims3) dz = zq - zi[p];
+                double r2 = __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2));
+                if constexpr (L::dims3) r2 = __builtin_fma(dz, dz, r2);
                 const double inv3 = rsqrt3_f64(r2, k15, k1875);
                 if constexpr (UM) {
                     ax[p] = __builtin_fma(inv3, dx, ax[p]);
                     ay[p] = __builtin_fma(inv3, dy, ay[p]);
-                    if constexpr (!DIAG) { aqx = __builtin_fma(-inv3, dx, aqx); aqy = __builtin_fma(-inv3, dy, aqy); }
+                    if constexpr (L::dims3) az[p] = __builtin_fma(inv3, dz, az[p]);
+                    if constexpr (!DIAG) {
+                        aqx = __builtin_fma(-inv3, dx, aqx);
+                        aqy = __builtin_fma(-inv3, dy, aqy);
+                        if constexpr (L::dims3) aqz = __builtin_fma(-inv3, dz, aqz);
+                    }
                 } else {
                     const double si = mq * inv3;
                     ax[p] = __builtin_fma(si, dx, ax[p]);
                     ay[p] = __builtin_fma(si, dy, ay[p]);
+                    if constexpr (L::dims3) az[p] = __builtin_fma(si, dz, az[p]);
                     if constexpr (!DIAG) {
                         const double sj = mi[p] * inv3;
                         aqx = __builtin_fma(-sj, dx, aqx);
                         aqy = __builtin_fma(-sj, dy, aqy);
+                        if constexpr (L::dims3) aqz = __builtin_fma(-sj, dz, aqz);
                     }
                 }
             }
             xq = xr; yq = yr;
+            if constexpr (L::dims3) zq = zr;
             if constexpr (!UM) mq = mr;
-            if constexpr (!DIAG) { aqx = lane_rot64(aqx, addr); aqy = lane_rot64(aqy, addr); }
+            if constexpr (!DIAG) {
+                aqx = lane_rot64(aqx, addr); aqy = lane_rot64(aqy, addr);
+                if constexpr (L::dims3) aqz = lane_rot64(aqz, addr);
+            }
         }
         if constexpr (!DIAG) {
-            double2 r = make_double2(aqx, aqy);
-            if constexpr (UM) { r.x *= um_mass; r.y *= um_mass; }
-            double2 (*rb)[64] = red[c & 1u];
+            typename L::vec r;
+            if constexpr (L::dims3) r = make_double4(aqx, aqy, aqz, 0.0); else r = make_double2(aqx, aqy);
+            if constexpr (UM) { r.x *= um_mass; r.y *= um_mass; if constexpr (L::dims3) r.z *= um_mass; }
+            typename L::vec (*rb)[64] = red[c & 1u];
             rb[w][lane] = r;
             __syncthreads();
             if (w == 0) {
                 const uint32_t j = (c0 + c) * SYM_CH + lane;
-                double2 a = rb[0][lane];
+                typename L::vec a = rb[0][lane];
 #pragma unroll
-                for (int k = 1; k < 4; ++k) { a.x += rb[k][lane].x; a.y += rb[k][lane].y; }
+                for (int k = 1; k < 4; ++k) { a.x += rb[k][lane].x; a.y += rb[k][lane].y; if constexpr (L::dims3) a.z += rb[k][lane].z; }
                 if (j < n) slab_r_row[j] = a;
             }
         }
         xq = xn; yq = yn;
+        if constexpr (L::dims3) zq = zn;
         if constexpr (!UM) mq = mn;
     }
 }
 
-template <bool UM>
+template <typename L, bool UM>
 __global__ __launch_bounds__(BLOCK)
-void force_sym_f64(const double2 *__restrict__ pos, const double *__restrict__ mass,
+void force_sym_f64(const typename L::vec *__restrict__ pos, const double *__restrict__ mass,
                    const SymItem *__restrict__ items,
-                   double2 *__restrict__ slab_s, double2 *__restrict__ slab_r,
+                   typename L::vec *__restrict__ slab_s, typename L::vec *__restrict__ slab_r,
                    uint32_t n, double eps2, double um_mass, uint32_t *ticket, uint32_t first_wave, uint32_t ticket_base)
 {
     static_assert(64 * SYM_P64 == SYM_WT, "fp64 and fp32 symmetric kernels share the tile geometry");
-    __shared__ double2 red[2][4][64];
+    __shared__ typename L::vec red[2][4][64];
     const SymItem it = items[sym_item_index(ticket, first_wave, ticket_base)];
     const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-    double xi[SYM_P64], yi[SYM_P64], mi[SYM_P64], ax[SYM_P64], ay[SYM_P64];
+    double xi[SYM_P64], yi[SYM_P64], zi[SYM_P64], mi[SYM_P64], ax[SYM_P64], ay[SYM_P64], az[SYM_P64];
     uint32_t li[SYM_P64];
 #pragma unroll
     for (int p = 0; p < SYM_P64; ++p) {
         li[p] = w * SYM_WT + (uint32_t)p * 64u + lane;
         const uint32_t g = it.tile * SYM_SB + li[p];
-        xi[p] = PAD_XY64; yi[p] = PAD_XY64; mi[p] = 0.0;
-        if (g < n) { const double2 q = pos[g]; xi[p] = q.x; yi[p] = q.y; if constexpr (!UM) mi[p] = mass[g]; }
-        ax[p] = 0.0; ay[p] = 0.0;
+        xi[p] = PAD_XY64; yi[p] = PAD_XY64; zi[p] = PAD_XY64; mi[p] = 0.0;
+        if (g < n) {
+            const auto q = pos[g]; xi[p] = q.x; yi[p] = q.y;
+            if constexpr (L::dims3) { zi[p] = q.z; mi[p] = q.w; } else if constexpr (!UM) mi[p] = mass[g];
+        }
+        ax[p] = 0.0; ay[p] = 0.0; az[p] = 0.0;
     }
-    double2 *__restrict__ rrow = slab_r + it.r_base;
-    if (it.diag) sym_chunks_f64<UM, true>(pos, mass, rrow, n, it.c0, it.cnt, xi, yi, mi, ax, ay, eps2, um_mass, red);
-    else         sym_chunks_f64<UM, false>(pos, mass, rrow, n, it.c0, it.cnt, xi, yi, mi, ax, ay, eps2, um_mass, red);
-    double2 *__restrict__ out = slab_s + (size_t)it.s_row * SYM_SB;
+    typename L::vec *__restrict__ rrow = slab_r + it.r_base;
+    if (it.diag) sym_chunks_f64<L, UM, true>(pos, mass, rrow, n, it.c0, it.cnt, xi, yi, zi, mi, ax, ay, az, eps2, um_mass, red);
+    else         sym_chunks_f64<L, UM, false>(pos, mass, rrow, n, it.c0, it.cnt, xi, yi, zi, mi, ax, ay, az, eps2, um_mass, red);
+    typename L::vec *__restrict__ out = slab_s + (size_t)it.s_row * SYM_SB;
 #pragma unroll
     for (int p = 0; p < SYM_P64; ++p) {
-        if constexpr (UM) { ax[p] *= um_mass; ay[p] *= um_mass; }
-        out[li[p]] = make_double2(ax[p], ay[p]);
+        if constexpr (UM) { ax[p] *= um_mass; ay[p] *= um_mass; az[p] *= um_mass; }
+        if constexpr (L::dims3) out[li[p]] = make_double4(ax[p], ay[p], az[p], 0.0);
+        else out[li[p]] = make_double2(ax[p], ay[p]);
     }
 }
 

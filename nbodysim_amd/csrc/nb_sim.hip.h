@@ -7,7 +7,6 @@
 #include "nbody_debug.h"
 #include "nb_internal.h"
 #include "nb_kernels.hip.h"
-#include "nb_kernels3d.hip.h"
 #include "nb_collide.hip.h"
 #include "nb_tree.hip.h"
 #include "nb_raster.hip.h"

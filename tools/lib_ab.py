@@ -10,7 +10,9 @@ in any order: o one-sided (symmetry=False), g eps = 0 (the guarded body, one-sid
 individual-masses run (uniform_mass=False, mass_scaling=True), c collisions (extras |= NB_EXTRA_COLLIDE, on the ref base: its bodies
 have radii); the Barnes-Hut force: t force="tree" at theta = 0.5, l tree_leaves=True,
 u tree_quadrupole=True, r tree_alpha=0.02, e tree_energy=True (the hash then also covers the two doubles of energy() read after the
-steps).  Example: og-qd4096, os-p65536, c-ref25000, tlur-p4096.  A combination Simulation rejects ends the run with its message.
+steps); the symmetric sweep: x sym_chunk_pairs=1 (the chunk-pair sweep, below the size that switches it on), y sym_chunks_per_item=3
+(an odd chunk count: with x, the last pair of an item is half empty).  Example: og-qd4096, os-p65536, c-ref25000, tlur-p4096,
+kxy-q16421.  A combination Simulation rejects ends the run with its message.
 
 (the Python binding loads $NBODY_HIP_LIB when set — the LIBRARY reads no environment variables; each side runs in a child process)
 
@@ -69,6 +71,10 @@ def child(cases, steps, pkg=None):
             kw["tree_alpha"] = 0.02
         if "e" in mods:
             kw["tree_energy"] = True
+        if "x" in mods:
+            kw["sym_chunk_pairs"] = 1
+        if "y" in mods:
+            kw["sym_chunks_per_item"] = 3
         for general in (False, True):
             k = dict(kw)
             if general:
