@@ -111,6 +111,30 @@ _Static_assert(offsetof(nb_tree_node, mass) == 16 && offsetof(nb_tree_node, cent
                "Node field offsets");
 #endif
 
+/* ---- group record ---------------------------------------------------------
+ * One friends-of-friends group as nb_group_catalog (below) reports it.  80 bytes, no padding. */
+typedef struct nb_group {
+    uint32_t label;         /* offset   0  smallest global body index of the group: nb_groups' label */
+    uint32_t members;       /* offset   4  bodies in the group: nb_groups' size */
+    double   mass;          /* offset   8  M = sum w_i */
+    double   pos[3];        /* offset  16  centre of mass, sum w_i x_i / W;  [2] = 0 on a 2-D handle */
+    double   vel[3];        /* offset  40  sum w_i v_i / W */
+    double   sigma2;        /* offset  64  sum w_i |v_i - vel|^2 / W: velocity dispersion */
+    double   r_max;         /* offset  72  max_i |x_i - pos|: the radius that holds the group */
+} nb_group;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_group) == 80, "nb_group is 80 bytes");
+static_assert(offsetof(nb_group, members) == 4 && offsetof(nb_group, mass) == 8 && offsetof(nb_group, pos) == 16 &&
+              offsetof(nb_group, vel) == 40 && offsetof(nb_group, sigma2) == 64 && offsetof(nb_group, r_max) == 72,
+              "nb_group field offsets");
+#else
+_Static_assert(sizeof(nb_group) == 80, "nb_group is 80 bytes");
+_Static_assert(offsetof(nb_group, members) == 4 && offsetof(nb_group, mass) == 8 && offsetof(nb_group, pos) == 16 &&
+               offsetof(nb_group, vel) == 40 && offsetof(nb_group, sigma2) == 64 && offsetof(nb_group, r_max) == 72,
+               "nb_group field offsets");
+#endif
+
 /* ---- enums ---------------------------------------------------------------- */
 enum { NB_OK = 0, NB_EINVAL = -1, NB_ENODEVICE = -2, NB_EHIP = -3, NB_ENOMEM = -4,
        NB_EIO = -5, NB_EFORMAT = -6, NB_ESTATE = -7 };
@@ -704,6 +728,55 @@ int nb_neighbors(nb_sim *s, float radius, uint32_t k, uint32_t *idx, float *dist
  * of a wave and of a workgroup that share a group: all 1 048 576 bodies in ONE group cost it 0.020 ms, one add per body 11.9 ms.
  * With nb_profile_enable the link kernel is bracketed like a force launch and counts as one (nb_profile_read). */
 int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *size, uint64_t *ngroups);
+
+/* The group catalogue: mass, centre, motion, velocity dispersion and radius of every friends-of-friends group of at least min_members
+ * bodies, reduced on the device; the answer is 80 bytes per GROUP (nb_group above).  Without it a caller takes nb_groups' labels,
+ * nb_syncs 64 B per body and runs a bincount pass on the host every frame.
+ * GROUPS: exactly nb_groups' at the same radius: its predicate, all n bodies of the current replica at the positions of all work
+ * enqueued so far, an NB_FP64 handle's positions rounded to float for the grouping, a dims = 3 handle grouped on its (x, y)
+ * projection, a body with a non-finite coordinate a group of its own.  The catalogue holds the groups with members >= min_members in
+ * ascending order of label; *count is their number.
+ * VALUES: x, v and m of a body are the float values nb_sync returns for it, widened to double (an NB_FP64 handle's are rounded to float
+ * first); on a dims = 3 handle z takes part in pos, vel, sigma2 and r_max.  w_i = m_i when m_i > 0, else 0.  mass = sum w_i.
+ * W = mass when mass > 0; otherwise every w_i = 1 and W = members (the unweighted means of a massless group; mass stays 0).  The
+ * products w_i x_i are exact in double (24 x 24 bits).  Every sum is fp64 in an order that is fixed for given bodies, radius and
+ * min_members: a segmented scan over the bodies sorted by (label, index); there is no floating-point atomic anywhere.  sigma2 and
+ * r_max come from a second pass about the finished vel / pos, not from raw second moments minus squares.  A group that holds a body
+ * with a non-finite value gets what the arithmetic gives.  CONSEQUENCES: two handles, and two calls on one handle, agree byte for byte;
+ * permuting the bodies relabels the groups (label is the smallest NEW index), leaves members exact and the double fields equal up to
+ * the order of summation: a sum of k terms differs from the exact one by at most about k 2^-53 sum |terms|.
+ * COUNT QUERY AND CAPACITY, as nb_tree_nodes: count may not be NULL; out == NULL writes *count and returns NB_OK (the passes that
+ * reduce are not run); out != NULL with capacity < *count is NB_EINVAL naming both numbers, *count is written and out is untouched.
+ * Only the first *count records of out are written.
+ * out may be any host memory: a range known to be page-locked (nb_host_alloc / nb_host_register) is written by the copy engine
+ * directly, anything else moves through the query calls' shared staging buffer (nb_tree_nodes), 80 B per group.
+ * ERRORS: NB_EINVAL, naming the argument, before any device work: a NULL handle; a NULL count; nb_groups' rules for the radius;
+ * min_members == 0.  NB_ESTATE while a split step is in flight.  NB_ESTATE on a handle that does not own all n bodies
+ * (nb_owned_count(s) < n: a block handle holds the velocities of its block only, and the catalogue is about whole groups); all-reduce
+ * and single-rank sharded handles own all n and are served.  The call synchronises; a pending once-only report leaves through it as
+ * through nb_groups (NB_ENOMEM, once): nothing is written then, *count included.  NB_EHIP, nothing written, if the union-find left
+ * its bound, as in nb_groups.
+ * Nothing of the handle changes: positions, velocities, acc[], frame counter, tree arrays and nb_tree_stats are untouched, and the
+ * next step is bit-identical to one on a handle that never called this.  nb_groups, nb_neighbors and this call share their scratch
+ * and may alternate on one handle at any radii.
+ * Memory: nothing until the first call; then (growth only, freed by nb_destroy) nb_groups' 44 bytes per body of the replica and sort
+ * storage, if those calls have not made them yet (the sort by label runs in the same arrays), plus 16 bytes per body (head flag,
+ * rank, length / row by label), the scan's temporary storage and 224 bytes per 1024 bodies (the carries); once a filling call has run,
+ * 184 bytes per group of the largest catalogue seen plus an eighth (the 13 sums and the record); the shared staging buffer is grown
+ * to 80 bytes per group once a destination needs it.  Nothing is sized by n that depends on the count.
+ * Cost: nb_groups' grouping, one more sort of n (label, index) pairs, and two reduction passes that are balanced over sorted
+ * positions, not over groups: a workgroup reduces a fixed run of 1024 consecutive positions with a head-flagged segmented scan, and a
+ * second, small launch adds the pieces of the groups that reach across runs, in run order.  All bodies in one group cost what all
+ * singletons cost.  On an MI355X, Plummer spheres, min_members 2, records into nb_host_alloc memory (profiles/group_catalog_bench.log): at
+ * 1 048 576 bodies with a mean of 1 / 5 / 31 links per body (145 091 / 73 466 / 28 567 groups in the catalogue) 0.94 / 1.44 / 2.69 ms,
+ * of which the two reduction passes 0.12 / 0.11 / 0.10 ms, where nb_groups(label, size) alone takes 0.59 / 1.30 / 2.62 ms and the host
+ * route (nb_groups' labels, nb_sync, numpy bincount with weights, one thread) 36 / 33 / 37 ms; the count query 0.58 / 1.23 / 2.54 ms;
+ * into a pageable array 1.23 / 1.60 / 2.78 ms; at 262 144 bodies 0.45 / 0.88 / 0.87 ms (host route 5.1 - 7.4); at 8 388 608 (tree
+ * handle, 1 148 923 / 565 389 / 227 560 groups) 5.20 / 5.67 / 7.98 ms (host route 314 - 327).  The reduction passes at 1 048 576 bodies
+ * with every body a singleton: 0.21 ms; with all bodies in ONE group: 0.09 ms.
+ * With nb_profile_enable the reduction passes (both, with their carry launches) are bracketed like a force launch and count as one
+ * (nb_profile_read); the link kernel is not bracketed in this call. */
+int nb_group_catalog(nb_sim *s, float radius, uint32_t min_members, nb_group *out, size_t capacity, size_t *count);
 
 /* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
  * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without

@@ -9,6 +9,7 @@ the first use does, and raises if it has not been built.
 from ._lib import (  # noqa: F401
     BODY3_DTYPE,
     BODY_DTYPE,
+    GROUP_DTYPE,
     NODE_DTYPE,
     NBodyError,
     PinnedBodies,
@@ -23,6 +24,7 @@ from .simulation import Simulation, read_bodies, write_bodies  # noqa: F401
 __all__ = [
     "BODY3_DTYPE",
     "BODY_DTYPE",
+    "GROUP_DTYPE",
     "NODE_DTYPE",
     "NBodyError",
     "PinnedBodies",

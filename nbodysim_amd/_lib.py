@@ -75,6 +75,17 @@ NODE_DTYPE = np.dtype(
 )
 
 
+#: numpy view of the 80-byte ``nb_group`` record of include/nbody.h, as ``nb_group_catalog`` fills it (no padding)
+GROUP_DTYPE = np.dtype(
+    {
+        "names": ["label", "members", "mass", "pos", "vel", "sigma2", "r_max"],
+        "formats": [np.uint32, np.uint32, np.float64, (np.float64, 3), (np.float64, 3), np.float64, np.float64],
+        "offsets": [0, 4, 8, 16, 40, 64, 72],
+        "itemsize": 80,
+    }
+)
+
+
 def nodes_array(n: int) -> np.ndarray:
     """Zero-initialised array of n 128-byte Node records (padding zero)."""
     return np.zeros(n * NODE_DTYPE.itemsize, dtype=np.uint8).view(NODE_DTYPE)
@@ -215,6 +226,7 @@ PROTOTYPES = {
     "nb_raster": (C.c_int, [C.c_void_p, C.POINTER(nb_view), C.c_void_p, C.c_void_p]),
     "nb_neighbors": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nb_groups": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "nb_group_catalog": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),
     "nb_owned_begin": (C.c_size_t, [C.c_void_p]),

@@ -1,6 +1,7 @@
 // nb_groups_host.hip.h — host side of nb_groups (kernels: nb_groups.hip.h).  Included by nb_capi.hip behind the neighbours' host, whose
 // front half it shares: neighbors_alloc for the per-body arrays and the sort's storage, neighbors_cells for the keys, the sort and the
 // gather.  It opens with query_enter and moves its planes with copy_plane through the query staging buffer, like nb_neighbors.
+// Its own front half (groups_labels, groups_fault) is shared with nb_group_catalog (nb_group_catalog_host.hip.h).
 #pragma once
 
 #ifdef NB_GROUPS_PLAIN_TALLY                   // A/B builds (tools/groups_bench.py): one global add per body in the size pass
@@ -30,6 +31,39 @@ static int groups_alloc(nb_sim *s, bool want_size)
     return NB_OK;
 }
 
+// The front half that nb_groups and nb_group_catalog share: the scratch, the cells, and the union-find down to the flattened labels.
+// Afterwards grp.parent[i] is the label of body i for all n bodies of the replica and grp.words[0] the fault word (still on the device:
+// the caller copies grp.words to grp.host behind its own launches, synchronises and asks groups_fault).
+static int groups_labels(nb_sim *s, float radius, float r2, bool want_size, bool profile_link)
+{
+    { const int rc = neighbors_alloc(s, 0, false, false, false); if (rc) return rc; }
+    { const int rc = groups_alloc(s, want_size); if (rc) return rc; }
+    nb_sim::Neighbors &q = s->nbr;
+    nb_sim::Groups &g = s->grp;
+    const uint32_t n = (uint32_t)s->n, blocks = (n + BLOCK - 1) / BLOCK;
+    HIPCHK(hipMemsetAsync(g.words, 0, 2 * sizeof(uint32_t), s->stream));
+    { const int rc = neighbors_cells(s, radius); if (rc) return rc; }
+    groups_init<<<blocks, BLOCK, 0, s->stream>>>(g.parent, n);
+    HIPCHK(hipGetLastError());
+    std::pair<hipEvent_t, hipEvent_t> pr;                         // nb_groups: with nb_profile_enable the link kernel counts as one launch
+    if (profile_link && s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
+    groups_link<<<blocks, BLOCK, 0, s->stream>>>(q.skey, q.sval, q.sxy, n, r2, g.parent, &g.words[0]);
+    HIPCHK(hipGetLastError());
+    if (profile_link && s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
+    groups_flatten<<<blocks, BLOCK, 0, s->stream>>>(g.parent, n, &g.words[0]);
+    HIPCHK(hipGetLastError());
+    return NB_OK;
+}
+
+// the fault word, once it has reached grp.host: cannot be set while parent[x] <= x holds (nb_groups.hip.h); nothing is written
+static int groups_fault(const nb_sim *s, const char *name)
+{
+    const uint32_t f = s->grp.host[0];
+    if (!f) return NB_OK;
+    return nb_fail(NB_EHIP, "%s: the union-find left its bound (%s): parent[] is no forest", name,
+                   f & GROUPS_FAULT_FIND ? "a find of more than n + 1 hops" : "a unite of more than n + 1 rounds");
+}
+
 // Which bodies form a clump: the friends-of-friends groups at linking length `radius`, labelled by their smallest body index.
 extern "C" int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *size, uint64_t *ngroups)
 {
@@ -39,23 +73,11 @@ extern "C" int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *siz
     { const int rc = check_radius("nb_groups", radius, &r2); if (rc) return rc; }
     { const int rc = query_enter(s, "nb_groups"); if (rc) return rc; }        // no snapshot wait, as in nb_neighbors
     const size_t bytes = s->i_count * sizeof(uint32_t);           // of either plane
-    { const int rc = neighbors_alloc(s, 0, false, false, false); if (rc) return rc; }
-    { const int rc = groups_alloc(s, size != nullptr); if (rc) return rc; }
     { const int rc = query_stage(s, std::max(stage_need(label, bytes), stage_need(size, bytes))); if (rc) return rc; }
+    { const int rc = groups_labels(s, radius, r2, size != nullptr, true); if (rc) return rc; }
     nb_sim::Neighbors &q = s->nbr;
     nb_sim::Groups &g = s->grp;
     const uint32_t n = (uint32_t)s->n, blocks = (n + BLOCK - 1) / BLOCK, ib = (uint32_t)s->i_begin, ic = (uint32_t)s->i_count;
-    HIPCHK(hipMemsetAsync(g.words, 0, 2 * sizeof(uint32_t), s->stream));
-    { const int rc = neighbors_cells(s, radius); if (rc) return rc; }
-    groups_init<<<blocks, BLOCK, 0, s->stream>>>(g.parent, n);
-    HIPCHK(hipGetLastError());
-    std::pair<hipEvent_t, hipEvent_t> pr;                         // with nb_profile_enable the link kernel counts as one launch
-    if (s->prof && prof_begin(s, &pr, nullptr)) return NB_EHIP;
-    groups_link<<<blocks, BLOCK, 0, s->stream>>>(q.skey, q.sval, q.sxy, n, r2, g.parent, &g.words[0]);
-    HIPCHK(hipGetLastError());
-    if (s->prof && prof_end(s, pr, nullptr, 1)) return NB_EHIP;
-    groups_flatten<<<blocks, BLOCK, 0, s->stream>>>(g.parent, n, &g.words[0]);
-    HIPCHK(hipGetLastError());
     if (ngroups) {
         groups_roots<<<std::min(blocks, 1024u), BLOCK, 0, s->stream>>>(g.parent, n, &g.words[1]);
         HIPCHK(hipGetLastError());
@@ -71,9 +93,7 @@ extern "C" int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *siz
     }
     HIPCHK(hipMemcpyAsync(g.host, g.words, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
-    if (g.host[0])                                                // cannot happen while parent[x] <= x holds (nb_groups.hip.h); nothing is written
-        return nb_fail(NB_EHIP, "nb_groups: the union-find left its bound (%s): parent[] is no forest",
-                       g.host[0] & GROUPS_FAULT_FIND ? "a find of more than n + 1 hops" : "a unite of more than n + 1 rounds");
+    { const int rc = groups_fault(s, "nb_groups"); if (rc) return rc; }
     if (label) {
         const int rc = copy_plane(s, label, g.parent + ib, bytes);
         if (rc) return rc;

@@ -13,6 +13,7 @@
 #include "nb_potential.hip.h"
 #include "nb_neighbors.hip.h"
 #include "nb_groups.hip.h"
+#include "nb_group_catalog.hip.h"
 #include "nb_order.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -254,6 +255,23 @@ struct nb_sim {
         uint32_t *words = nullptr;             // device: the fault word, the number of groups
         uint32_t *host = nullptr;              // page-locked mirror of the two
     } grp;
+
+    // nb_group_catalog (nb_group_catalog.hip.h): nothing in `cat` exists before the first call; the labels are `grp`'s, the sort's
+    // arrays and storage `nbr`'s (key / skey / val / sval are free again once the link kernel has run)
+    struct GroupCatalog {
+        uint64_t cap = 0;                      // the three per-body arrays hold cap entries: n + 1 from the first call on
+        uint32_t *flag = nullptr;              // 1 at the head of a group that is kept ...
+        uint64_t *rank = nullptr;              // ... and the prefix sum: its row; rank[n] is the count
+        uint32_t *len_row = nullptr;           // by label: the group's length, then its row (CATALOG_NO_ROW: not kept)
+        void *tmp = nullptr;                   // rocprim temporary storage of the scan (asked for n + 1 elements)
+        size_t tmp_bytes = 0;
+        uint64_t slot_cap = 0;                 // carry slots: two per run of CATALOG_RUN sorted positions
+        CatalogSlot *slot = nullptr;
+        uint64_t rec_cap = 0;                  // groups `sums` and `rec` hold: grown by the count of a filling call, not by n
+        CatalogSums *sums = nullptr;
+        nb_group *rec = nullptr;
+        uint64_t *host = nullptr;              // page-locked: the count
+    } cat;
 
     // body order of the whole-system symmetric path (nb_order.hip.h): nothing in `ord` is allocated unless `on`
     struct Order {

@@ -359,6 +359,28 @@ class Simulation:
         out = (label,) + ((sizes,) if size else ()) + ((int(count.value),) if ngroups else ())
         return out[0] if len(out) == 1 else out
 
+    def group_catalog(self, radius: float, min_members: int = 2, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The catalogue of the friends-of-friends groups at linking length ``radius`` with at least ``min_members`` bodies, reduced on
+        the device (``nb_group_catalog``; synchronises): a ``GROUP_DTYPE`` array in ascending order of ``label`` with ``members``,
+        ``mass``, the centre of mass ``pos``, the mean velocity ``vel``, the velocity dispersion ``sigma2`` and the radius ``r_max`` of
+        every group (include/nbody.h has the definitions).  The count is queried first, then the records are filled.  ``out``: a
+        writeable C-contiguous 1-D ``GROUP_DTYPE`` array that holds at least that many records (one over ``nb_host_alloc`` memory is
+        written by the copy engine directly); the view of its filled part is returned; default a new array.  The handle must own all
+        n bodies."""
+        if not 1 <= min_members <= 0xFFFFFFFF:
+            raise ValueError(f"group_catalog: min_members must be 1 .. 2^32 - 1 (got {min_members})")
+        if out is not None and (not isinstance(out, np.ndarray) or out.dtype != L.GROUP_DTYPE or out.ndim != 1 or not out.flags.c_contiguous
+                                or not out.flags.writeable):
+            raise TypeError("out must be a writeable C-contiguous 1-D numpy array of nbodysim_amd.GROUP_DTYPE (80-byte nb_group records)")
+        cnt = C.c_size_t()
+        L.check("nb_group_catalog", self._lib.nb_group_catalog(self._h, radius, min_members, None, 0, C.byref(cnt)), self._lib)
+        if out is None:
+            out = np.zeros(cnt.value, dtype=L.GROUP_DTYPE)
+        if cnt.value:
+            L.check("nb_group_catalog", self._lib.nb_group_catalog(self._h, radius, min_members, out.ctypes.data, out.shape[0], C.byref(cnt)),
+                    self._lib)
+        return out[: cnt.value]
+
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
         L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)
