@@ -778,6 +778,58 @@ int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *size, uint64_t
  * (nb_profile_read); the link kernel is not bracketed in this call. */
 int nb_group_catalog(nb_sim *s, float radius, uint32_t min_members, nb_group *out, size_t capacity, size_t *count);
 
+/* The histogram of pair separations, DD(r): how many unordered pairs of bodies lie in each of nbins distance bins, counted on the
+ * device; the answer is at most 64 integers however many bodies there are.  It is the raw material of the two-point correlation
+ * function xi(r), the radial distribution function g(r) and a correlation dimension (INTEGRATION.md has the recipe).  Without it a
+ * caller takes nb_neighbors' rows, which k <= 32 truncates exactly in the dense regions, or nb_syncs 8 - 64 B per body and runs a tree
+ * or grid pass on the host every frame.
+ * BINS: edges holds nbins + 1 floats, 1 <= nbins <= NB_PAIR_BINS_MAX.  e2[t] = edges[t] * edges[t], one fp32 multiply on the host, and
+ * r2max = e2[nbins].  Bin b holds the pairs with e2[b] <= d2 < e2[b + 1]: closed below, open above.  counts[b] is exact, 64-bit; only
+ * the nbins entries of counts are written.
+ * PAIRS: d2 is nb_neighbors' predicate word for word: fp32, one rounding per operation, no contraction,
+ *     dx = x_j - x_i      dy = y_j - y_i      d2 = dx * dx + dy * dy
+ * Every unordered pair {i, j}, i != j, is counted once (d2(i, j) = d2(j, i) bit for bit).  Bodies on one position are a pair at
+ * d2 = 0: counted in bin 0 when edges[0] == 0, in no bin otherwise.  Massless bodies take part.  A body with a non-finite coordinate
+ * is in no pair; a pair whose d2 overflows to +inf is in no bin.
+ * WHICH BODIES: nb_neighbors' rules.  All n bodies of the CURRENT replica (on a sharded handle it must be complete, as for nb_energy),
+ * at the positions of all work enqueued so far, exactly as nb_sync_positions defines them.  An NB_FP64 handle's positions are rounded
+ * to float first; a dims = 3 handle is projected on (x, y).  Every kind of handle: direct or tree, any flags, sharded or not.  A handle
+ * that owns [i_begin, i_begin + i_count) counts the pairs whose LOWER global index lies in its block, nb_energy's convention: the
+ * counts of the ranks of a sharded run add up to the unsharded counts; an all-reduce or single-rank handle owns all n and returns the
+ * total.  CONSEQUENCES: the counts are integers and do not depend on the order of the sweep: two handles, and two calls on one
+ * handle, agree bit for bit; permuting the bodies leaves every count unchanged on a handle that owns all n; and the counts add up to
+ * n_finite (n_finite - 1) / 2, n_finite the bodies with finite coordinates, when edges[0] == 0 and r2max exceeds every d2.
+ * ERRORS: NB_EINVAL, naming the argument and the offending index, before any device work, in this order: a NULL handle, edges or
+ * counts; nbins outside 1 .. 64; a non-finite edge; edges[0] < 0 (-0 is 0); edges not strictly ascending; e2[t] >= e2[t + 1] for some
+ * t (edges whose squares tie or vanish in fp32, such as 1e-30f and 2e-30f, are refused: an empty or inverted bin is not silently
+ * produced); r2max not finite or 0 (nb_neighbors' rule for its radius, applied to edges[nbins]).  NB_ESTATE while a split step is in
+ * flight.  The call synchronises; a pending once-only report (collision capacity, failed tree build) leaves through it as through
+ * nb_neighbors (NB_ENOMEM, once), and nothing is written to counts then.
+ * Nothing of the handle changes: positions, velocities, acc[], frame counter, tree arrays and nb_tree_stats are untouched, and the
+ * next step is bit-identical to one on a handle that never called this.  nb_neighbors, nb_groups, nb_group_catalog and this call
+ * share the cell scratch and may alternate on one handle at any radii.
+ * Memory: nothing until the first call; then (growth only, freed by nb_destroy) nb_neighbors' 40 bytes per body of the replica and its
+ * sort storage, if that call has not made them yet; one row of 65 64-bit partials per workgroup of the count kernel, at most 8
+ * workgroups per compute unit (sized by the launch, not by n: 1.02 MiB on an MI355X); 65 words on the device and 65 page-locked ones.
+ * No staging buffer: the answer is at most 520 bytes.
+ * Cost: the bodies are sorted by the cell of a grid of cell size edges[nbins] x (1 + 2^-16) and every unordered pair of bodies in the
+ * same or adjacent cells is tested once (half the pairs nb_neighbors tests), each against every edge of the bin capacity in use (8,
+ * 16, 32 or 64, the smallest that holds nbins): the cost is proportional to those pairs times that capacity.  A last edge that
+ * covers the system is the n^2 sweep.  The caller chooses the edges.  On an MI355X, Plummer spheres, last edge for a mean of
+ * 5 / 31 neighbours per body, the whole call (profiles/pair_counts_bench.log): at 1 048 576 bodies 8 bins 0.31 / 0.35 ms, 16 bins 0.32 /
+ * 0.39 ms, 64 bins 0.66 / 1.30 ms, of which the count kernel 0.07 / 0.12, 0.08 / 0.16 and 0.43 / 1.06 ms, where the yardstick,
+ * nb_neighbors' count-only call at the same radius on the same handle, takes 0.59 / 0.61 ms (its search kernel 0.13 / 0.14 ms, and it
+ * copies 4 bytes per body out); at 262 144 bodies 16 bins 0.18 / 0.20 ms (64 bins 0.27 / 0.46; count-only call 0.26 / 0.29); at
+ * 8 388 608 (tree handle) 16 bins 1.53 / 1.99 ms, 64 bins 4.08 / 8.58 ms (count-only call 3.77 / 3.79).  The count kernel of capacity
+ * 64 takes 3.4 - 7.1 times that of capacity 16 for 3.8 times the edges: its 65 counters leave 2 waves per SIMD and its edges no longer
+ * fit the scalar registers ("Pair counts").  16 384 bodies in ONE cell, 16 bins: 2.4 ms, 5.6e10 pairs per second.
+ * The per-lane build's count kernel is within 0.02 ms of the cooperative one at 8 and 16 bins on these spheres (faster in seven rows
+ * of eight) and 1.4 - 1.5 times slower at 64.  A binary search with a per-wave LDS histogram in place of the cumulative counters has
+ * not been tried; neither has the capacity of 32 been timed.
+ * With nb_profile_enable the count kernel is bracketed like a force launch and counts as one (nb_profile_read). */
+#define NB_PAIR_BINS_MAX 64
+int nb_pair_counts(nb_sim *s, const float *edges, uint32_t nbins, uint64_t *counts);
+
 /* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
  * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without
  * the flag.  At creation alpha is 0.005: GADGET-2's customary ErrTolForceAcc, not a number measured for this library.  A setter

@@ -227,6 +227,7 @@ PROTOTYPES = {
     "nb_neighbors": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nb_groups": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "nb_group_catalog": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "nb_pair_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),
     "nb_owned_begin": (C.c_size_t, [C.c_void_p]),

@@ -1,7 +1,8 @@
 // nb_sim.hip.h — the handle behind the C ABI, and what every piece of host code around it needs: the HIP error check, the
 // device binding, the dispatchers from run-time choices to template arguments.  Included by nb_capi.hip (the one device
 // translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h, nb_raster_host.hip.h,
-// nb_potential_host.hip.h, nb_neighbors_host.hip.h, nb_groups_host.hip.h and nb_order_host.hip.h.
+// nb_potential_host.hip.h, nb_neighbors_host.hip.h, nb_groups_host.hip.h, nb_group_catalog_host.hip.h, nb_pair_counts_host.hip.h and
+// nb_order_host.hip.h.
 #pragma once
 #include "nbody.h"
 #include "nbody_debug.h"
@@ -14,6 +15,7 @@
 #include "nb_neighbors.hip.h"
 #include "nb_groups.hip.h"
 #include "nb_group_catalog.hip.h"
+#include "nb_pair_counts.hip.h"
 #include "nb_order.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -272,6 +274,14 @@ struct nb_sim {
         nb_group *rec = nullptr;
         uint64_t *host = nullptr;              // page-locked: the count
     } cat;
+
+    // nb_pair_counts (nb_pair_counts.hip.h): nothing in `pairs` exists before the first call; the cells and the sort are `nbr`'s
+    struct PairCounts {
+        uint64_t cap = 0;                      // words `partial` holds: 65 per workgroup of the largest count launch seen
+        uint64_t *partial = nullptr;           // one row of cumulative 64-bit counters per workgroup
+        uint64_t *words = nullptr;             // device: the 65 cumulative counters, the rows added up
+        uint64_t *host = nullptr;              // page-locked mirror of them
+    } pairs;
 
     // body order of the whole-system symmetric path (nb_order.hip.h): nothing in `ord` is allocated unless `on`
     struct Order {

@@ -245,6 +245,13 @@ public:
     {
         check(nb_groups(sim_, radius, label, size, ngroups), "nb_groups");
     }
+    // The histogram of pair separations (nb_pair_counts, include/nbody.h), at the positions of the work enqueued so far: counts[b] is
+    // the number of unordered pairs of bodies with edges[b] <= distance < edges[b + 1] (squares compared in float); edges holds
+    // nbins + 1 ascending values, counts nbins entries, nbins <= NB_PAIR_BINS_MAX.
+    void pair_counts(const float *edges, uint32_t nbins, uint64_t *counts)
+    {
+        check(nb_pair_counts(sim_, edges, nbins, counts), "nb_pair_counts");
+    }
     nb_sim *handle() { return sim_; }
 
 private:

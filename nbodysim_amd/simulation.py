@@ -381,6 +381,19 @@ class Simulation:
                     self._lib)
         return out[: cnt.value]
 
+    def pair_counts(self, edges) -> np.ndarray:
+        """The histogram of pair separations DD(r), counted on the device (``nb_pair_counts``; synchronises): ``edges`` are the
+        ``nbins + 1`` strictly ascending bin edges, 1 <= nbins <= 64, passed on as float32; bin b holds the unordered pairs {i, j} with
+        ``edges[b]**2 <= dx*dx + dy*dy < edges[b+1]**2`` in fp32, each pair once.  Returns the ``(nbins,)`` uint64 counts, exact.  A
+        handle that owns a block counts the pairs whose lower global index lies in it, so the counts of the ranks of a sharded run
+        add up to the whole.  The edges are validated by the library (include/nbody.h has the rules)."""
+        e = np.ascontiguousarray(edges, dtype=np.float32)
+        if e.ndim != 1 or e.size < 2:
+            raise ValueError("pair_counts: edges must be a 1-D sequence of at least two values")
+        counts = np.zeros(e.size - 1, dtype=np.uint64)
+        L.check("nb_pair_counts", self._lib.nb_pair_counts(self._h, e.ctypes.data, e.size - 1, counts.ctypes.data), self._lib)
+        return counts
+
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
         L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)
