@@ -135,6 +135,30 @@ _Static_assert(offsetof(nb_group, members) == 4 && offsetof(nb_group, mass) == 8
                "nb_group field offsets");
 #endif
 
+/* ---- group energy record --------------------------------------------------
+ * One friends-of-friends group as nb_group_binding (below) reports it: row r describes the group of row r of nb_group_catalog.
+ * 32 bytes, no padding. */
+typedef struct nb_group_energy {
+    uint32_t label;         /* offset   0  nb_group_catalog's label */
+    uint32_t members;       /* offset   4  nb_group_catalog's members */
+    uint32_t bound;         /* offset   8  members with e < 0 */
+    uint32_t most_bound;    /* offset  12  global index of the member with the smallest e; NB_NO_NEIGHBOR if no member's e compares */
+    double   e_min;         /* offset  16  its e; +inf with NB_NO_NEIGHBOR */
+    double   potential;     /* offset  24  U = 1/2 sum w_i phi[i] over the members: the group's self-potential energy */
+} nb_group_energy;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_group_energy) == 32, "nb_group_energy is 32 bytes");
+static_assert(offsetof(nb_group_energy, members) == 4 && offsetof(nb_group_energy, bound) == 8 && offsetof(nb_group_energy, most_bound) == 12 &&
+              offsetof(nb_group_energy, e_min) == 16 && offsetof(nb_group_energy, potential) == 24,
+              "nb_group_energy field offsets");
+#else
+_Static_assert(sizeof(nb_group_energy) == 32, "nb_group_energy is 32 bytes");
+_Static_assert(offsetof(nb_group_energy, members) == 4 && offsetof(nb_group_energy, bound) == 8 && offsetof(nb_group_energy, most_bound) == 12 &&
+               offsetof(nb_group_energy, e_min) == 16 && offsetof(nb_group_energy, potential) == 24,
+               "nb_group_energy field offsets");
+#endif
+
 /* ---- enums ---------------------------------------------------------------- */
 enum { NB_OK = 0, NB_EINVAL = -1, NB_ENODEVICE = -2, NB_EHIP = -3, NB_ENOMEM = -4,
        NB_EIO = -5, NB_EFORMAT = -6, NB_ESTATE = -7 };
@@ -777,6 +801,72 @@ int nb_groups(nb_sim *s, float radius, uint32_t *label, uint32_t *size, uint64_t
  * With nb_profile_enable the reduction passes (both, with their carry launches) are bracketed like a force launch and count as one
  * (nb_profile_read); the link kernel is not bracketed in this call. */
 int nb_group_catalog(nb_sim *s, float radius, uint32_t min_members, nb_group *out, size_t capacity, size_t *count);
+
+/* Unbinding: the potential of every body due to the OTHER MEMBERS OF ITS OWN friends-of-friends group, its energy in the group's rest
+ * frame, and per group how many members are bound, which one is the most bound (the group's centre) and the group's self-potential
+ * energy (with nb_group_catalog's mass x sigma2, the virial ratio: INTEGRATION.md has the recipe).  nb_potentials is the potential of the
+ * whole system, the wrong quantity for unbinding; without this call a caller takes nb_groups' labels, nb_syncs 64 B per body and runs an
+ * O(n_g^2) pass per group on the host.
+ * GROUPS AND ROWS: exactly nb_group_catalog's at the same radius and min_members.  Row r of out describes the group of row r of the
+ * catalogue: same label, same members, same order, same *count.
+ * PLANES: phi and e hold n doubles each, indexed by body.  For a body i of a kept group G
+ *     phi[i] = - sum_{j in G, j != i} m_j / sqrt(|x_j - x_i|^2 + eps^2)        e[i] = 1/2 |v_i - vel_G|^2 + phi[i]
+ * vel_G is the vel of the catalogue's record, bit for bit; v_i and the weights w_i are taken as the catalogue takes them (the float
+ * values widened to double, w_i = m_i > 0 ? m_i : 0).  On a dims = 3 handle z takes part in the distance and in |v - vel|^2; the grouping
+ * stays the (x, y) projection.  A body whose group is not kept gets a quiet NaN in both planes.  The self term is left out by INDEX,
+ * never by distance: members on one position each add -m_j / eps, and with eps = 0 only those bodies get values that are not finite.  A
+ * singleton kept with min_members = 1 has phi = +0 and e = +0.
+ * ARITHMETIC of phi: nb_potentials' rules inside the group; eps^2 is squared as the force launch squares it.  NB_FP32 handles: fp32
+ * displacement, r^2 by fused multiply-adds onto eps^2, v_rsq_f32, the terms m_j * inv added by FMA into fp32 runs of at most 64 terms, the
+ * runs added in fp64, the result fp64.  That gives nb_potentials' bar, which is derived and not measured: within 4e-6 relative of the fp64
+ * sum of the same float values for masses >= 0.  NB_FP64 handles: fp64 throughout from the handle's own positions and masses, the terms
+ * in the order of the sorted members (ascending body index).  THE ORDER of every sum is a function of the labels and n alone: the bodies
+ * are sorted by (label, index), the sorted positions are cut into runs [64 k, 64 k + 64), an fp32 run sums the members of i's group
+ * inside one run in ascending position, and the runs are added in ascending k (tests/group_binding_model.py).
+ * RECORDS: bound, most_bound, e_min and potential come from one head-flagged segmented scan over the sorted order, fp64, no float atomic.
+ * bound counts e < 0.  The argmin keeps the earlier position unless the later e is strictly smaller: ties go to the smallest body index,
+ * a NaN e is never chosen, and a group none of whose e is below +inf reports NB_NO_NEIGHBOR and e_min = +inf.
+ * COUNT QUERY AND CAPACITY: count may not be NULL.  With phi, e and out all NULL the call is the count query: NB_OK, *count written, the
+ * sweep not run, the cost that of nb_group_catalog's count query.  out != NULL with capacity < *count is NB_EINVAL naming both numbers;
+ * *count is written and nothing else.  Any of phi, e, out may be NULL on its own: a plane that is not asked for is not copied and not
+ * written; the sweep runs if any of the three is asked for.  Only the first *count records of out are written.
+ * CONSEQUENCES: two handles, and two calls on one handle, agree byte for byte.  Permuting the bodies relabels the groups and permutes the
+ * planes, leaves members exact, leaves bound and most_bound equal wherever no e is within rounding of 0 or of the minimum, and changes
+ * the doubles through the order of summation only.
+ * WHICH HANDLES: every handle nb_group_catalog serves: fp32 and fp64, dims 2 and 3, direct and tree with any flags, all-reduce and
+ * single-rank sharded handles.  NB_ESTATE, with the catalogue's message, on a handle with nb_owned_count(s) < n.
+ * ERRORS: NB_EINVAL, naming the argument, before any device work: a NULL handle; a NULL count; nb_groups' rules for the radius;
+ * min_members == 0.  NB_ESTATE while a split step is in flight.  The call synchronises; a pending once-only report leaves through it as
+ * through nb_groups (NB_ENOMEM, once): nothing is written then, *count included.  NB_EHIP, nothing written, if the union-find left its
+ * bound, as in nb_groups.
+ * Nothing of the handle changes: positions, velocities, acc[], frame counter, tree arrays and nb_tree_stats are untouched, and the next
+ * step is bit-identical to one on a handle that never called this.  It may alternate with nb_neighbors, nb_groups, nb_group_catalog and
+ * nb_pair_counts on one handle at any radii.
+ * phi, e and out may be any host memory: ranges known to be page-locked (nb_host_alloc / nb_host_register) are written by the copy engine
+ * directly, anything else moves through the query calls' shared staging buffer.
+ * Memory: nothing until the first call; the count query makes what nb_group_catalog's makes.  From the first filling call on (growth
+ * only, freed by nb_destroy) 48 bytes per body of the replica on an fp32 handle, 64 on an fp64 one (the body's record in sorted order
+ * 16 / 32, its segment 8, phi in sorted order 8, the two planes 16); per group of the largest catalogue seen plus an eighth, the
+ * catalogue's 184 bytes and 32 for the record; the shared staging buffer is grown to 8 bytes per body or 32 per group once a
+ * destination needs it.  Nothing sized by n depends on the count.
+ * Cost: nb_group_catalog's front half (grouping, sort by label, pass A for vel), then a sweep proportional to the sum of n_g^2 over the
+ * kept groups.  A linking length that percolates makes it the n^2 sweep: the caller chooses the radius, and nb_group_catalog's members
+ * tells the cost beforehand.  A workgroup owns a tile of T = 512 consecutive sorted positions and walks the union of their segments
+ * in LDS chunks; inside a giant group the chunks run nb_potentials' unmasked pair body, and only the two tiles at a segment's ends
+ * evaluate pairs for foreign lanes: at most sum_g 2 T n_g wasted lane-pairs, T the tile.  On an MI355X, Plummer spheres, min_members 2,
+ * e and records into nb_host_alloc memory (profiles/group_binding_bench.log; DESIGN.md section 6, "Group binding"): at 1 048 576 bodies
+ * with a mean of 1 / 5 / 31 links per body (largest group 192 / 463 238 / 831 606; sum n_g^2 3.9e6 / 2.1e11 / 6.9e11) 1.06 / 44.1 /
+ * 117.2 ms, of which the sweep 0.07 / 42.6 / 114.3 ms (5.0e12 / 6.1e12 pairs per second in the last two), where nb_group_catalog takes
+ * 0.93 / 1.46 / 2.71 ms and the count query 0.56 / 1.22 / 2.54 ms; into pageable arrays 0.2 - 0.3 ms more; at 262 144 bodies 0.52 / 5.85 /
+ * 13.2 ms (the host route at 1 link: nb_groups' labels, nb_sync, numpy per group, 528 ms); at 8 388 608 (tree handle) 6.17 ms at 1 link,
+ * and the two percolated radii (sum n_g^2 1.5e13 / 4.3e13) were not run.  THE YARDSTICK: on a handle whose 262 144 bodies are ONE group
+ * the sweep takes 10.60 ms where nb_potentials' direct sweep of the same pairs takes 9.80 ms, a ratio of 1.08; with 16 384 bodies in one
+ * cell 0.61 against 0.18 ms: 32 workgroups, so a giant group in a SMALL system underfills the chip (a smaller tile has not been
+ * written).  1 048 576 singletons / 524 288 pairs, min_members 1: 1.57 / 1.31 ms beside the catalogue's 2.21 / 1.49 ms.
+ * With nb_profile_enable the sweep is bracketed like a force launch and counts as one (nb_profile_read); the count query brackets
+ * nothing. */
+int nb_group_binding(nb_sim *s, float radius, uint32_t min_members, double *phi, double *e,
+                     nb_group_energy *out, size_t capacity, size_t *count);
 
 /* The histogram of pair separations, DD(r): how many unordered pairs of bodies lie in each of nbins distance bins, counted on the
  * device; the answer is at most 64 integers however many bodies there are.  It is the raw material of the two-point correlation

@@ -10,6 +10,7 @@ from ._lib import (  # noqa: F401
     BODY3_DTYPE,
     BODY_DTYPE,
     GROUP_DTYPE,
+    GROUP_ENERGY_DTYPE,
     NODE_DTYPE,
     NBodyError,
     PinnedBodies,
@@ -25,6 +26,7 @@ __all__ = [
     "BODY3_DTYPE",
     "BODY_DTYPE",
     "GROUP_DTYPE",
+    "GROUP_ENERGY_DTYPE",
     "NODE_DTYPE",
     "NBodyError",
     "PinnedBodies",

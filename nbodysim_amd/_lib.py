@@ -86,6 +86,17 @@ GROUP_DTYPE = np.dtype(
 )
 
 
+#: numpy view of the 32-byte ``nb_group_energy`` record of include/nbody.h, as ``nb_group_binding`` fills it (no padding)
+GROUP_ENERGY_DTYPE = np.dtype(
+    {
+        "names": ["label", "members", "bound", "most_bound", "e_min", "potential"],
+        "formats": [np.uint32, np.uint32, np.uint32, np.uint32, np.float64, np.float64],
+        "offsets": [0, 4, 8, 12, 16, 24],
+        "itemsize": 32,
+    }
+)
+
+
 def nodes_array(n: int) -> np.ndarray:
     """Zero-initialised array of n 128-byte Node records (padding zero)."""
     return np.zeros(n * NODE_DTYPE.itemsize, dtype=np.uint8).view(NODE_DTYPE)
@@ -227,6 +238,7 @@ PROTOTYPES = {
     "nb_neighbors": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nb_groups": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "nb_group_catalog": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "nb_group_binding": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nb_pair_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),

@@ -1,7 +1,7 @@
 // nb_sim.hip.h — the handle behind the C ABI, and what every piece of host code around it needs: the HIP error check, the
 // device binding, the dispatchers from run-time choices to template arguments.  Included by nb_capi.hip (the one device
 // translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h, nb_raster_host.hip.h,
-// nb_potential_host.hip.h, nb_neighbors_host.hip.h, nb_groups_host.hip.h, nb_group_catalog_host.hip.h, nb_pair_counts_host.hip.h and
+// nb_potential_host.hip.h, nb_neighbors_host.hip.h, nb_groups_host.hip.h, nb_group_catalog_host.hip.h, nb_group_binding_host.hip.h, nb_pair_counts_host.hip.h and
 // nb_order_host.hip.h.
 #pragma once
 #include "nbody.h"
@@ -15,6 +15,7 @@
 #include "nb_neighbors.hip.h"
 #include "nb_groups.hip.h"
 #include "nb_group_catalog.hip.h"
+#include "nb_group_binding.hip.h"
 #include "nb_pair_counts.hip.h"
 #include "nb_order.hip.h"
 
@@ -274,6 +275,19 @@ struct nb_sim {
         nb_group *rec = nullptr;
         uint64_t *host = nullptr;              // page-locked: the count
     } cat;
+
+    // nb_group_binding (nb_group_binding.hip.h): nothing in `gbind` exists before the first filling call; groups, sort, rows and means
+    // are `cat`'s, and the start of a segment by label lives in cat.flag behind catalog_rows
+    struct GroupBinding {
+        uint64_t cap = 0;                      // bodies the four per-body arrays hold: n from the first filling call on
+        uint2 *seg = nullptr;                  // by sorted position: {start, length} of its segment; length 0: the group is not kept
+        double *sphi = nullptr;                // phi by sorted position
+        double *phi = nullptr, *e = nullptr;   // the two planes by body
+        uint64_t rec_bytes = 0;                // bytes `srec` holds: n j-records in sorted order, 16 B (fp32 handle) or 32 B (fp64)
+        void *srec = nullptr;
+        uint64_t out_cap = 0;                  // records `out` holds: cat.rec_cap of the largest filling call
+        nb_group_energy *out = nullptr;
+    } gbind;
 
     // nb_pair_counts (nb_pair_counts.hip.h): nothing in `pairs` exists before the first call; the cells and the sort are `nbr`'s
     struct PairCounts {

@@ -245,6 +245,17 @@ public:
     {
         check(nb_groups(sim_, radius, label, size, ngroups), "nb_groups");
     }
+    // Unbinding (nb_group_binding, include/nbody.h), at the positions of the work enqueued so far: for every group of groups(radius)
+    // with at least min_members bodies, phi[i] = the potential of bodies[i] due to the other members of its own group and e[i] = its
+    // energy in the group's rest frame (bound when e[i] < 0; NaN for a body of a smaller group), and one nb_group_energy per group:
+    // bound members, the most bound one (the centre), the self-potential energy.  phi and e hold bodies.size() doubles, out `capacity`
+    // records; any may be null; all three null asks for the number of groups only.  Returns that number.
+    size_t group_binding(float radius, uint32_t min_members, double *phi, double *e, nb_group_energy *out, size_t capacity)
+    {
+        size_t count = 0;
+        check(nb_group_binding(sim_, radius, min_members, phi, e, out, capacity, &count), "nb_group_binding");
+        return count;
+    }
     // The histogram of pair separations (nb_pair_counts, include/nbody.h), at the positions of the work enqueued so far: counts[b] is
     // the number of unordered pairs of bodies with edges[b] <= distance < edges[b + 1] (squares compared in float); edges holds
     // nbins + 1 ascending values, counts nbins entries, nbins <= NB_PAIR_BINS_MAX.

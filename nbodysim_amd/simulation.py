@@ -381,6 +381,27 @@ class Simulation:
                     self._lib)
         return out[: cnt.value]
 
+    def group_binding(self, radius: float, min_members: int = 2, phi: bool = False, e: bool = True, records: bool = True):
+        """Unbinding on the device (``nb_group_binding``; synchronises), for the groups of ``group_catalog(radius, min_members)``:
+        ``phi[i]``, the potential of body i due to the other members of its own group; ``e[i] = |v_i - vel_G|^2 / 2 + phi[i]``, its
+        energy in the group's rest frame (bound when ``e[i] < 0``); both ``(n,)`` float64, NaN for a body whose group is not kept; and a
+        ``GROUP_ENERGY_DTYPE`` array, row r for the group of row r of the catalogue: ``label``, ``members``, ``bound``, ``most_bound``
+        (the global index of the member with the smallest e: the group's centre), ``e_min`` and ``potential`` (the self-potential
+        energy).  Returns what was asked for, in the order phi, e, records: one array, or a tuple; with none of the three the number
+        of groups.  The count is queried first, then one filling call runs the sweep.  The handle must own all n bodies."""
+        if not 1 <= min_members <= 0xFFFFFFFF:
+            raise ValueError(f"group_binding: min_members must be 1 .. 2^32 - 1 (got {min_members})")
+        cnt = C.c_size_t()
+        L.check("nb_group_binding", self._lib.nb_group_binding(self._h, radius, min_members, None, None, None, 0, C.byref(cnt)), self._lib)
+        if not (phi or e or records):
+            return int(cnt.value)
+        planes = [np.empty(self.n, dtype=np.float64) if want else None for want in (phi, e)]
+        rec = np.zeros(cnt.value, dtype=L.GROUP_ENERGY_DTYPE) if records else None
+        L.check("nb_group_binding", self._lib.nb_group_binding(self._h, radius, min_members, *(a.ctypes.data if a is not None else None for a in planes),
+                                                               rec.ctypes.data if records and cnt.value else None, cnt.value, C.byref(cnt)), self._lib)
+        out = tuple(a for a in planes if a is not None) + ((rec[: cnt.value],) if records else ())
+        return out[0] if len(out) == 1 else out
+
     def pair_counts(self, edges) -> np.ndarray:
         """The histogram of pair separations DD(r), counted on the device (``nb_pair_counts``; synchronises): ``edges`` are the
         ``nbins + 1`` strictly ascending bin edges, 1 <= nbins <= 64, passed on as float32; bin b holds the unordered pairs {i, j} with
