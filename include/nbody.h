@@ -135,6 +135,32 @@ _Static_assert(offsetof(nb_group, members) == 4 && offsetof(nb_group, mass) == 8
                "nb_group field offsets");
 #endif
 
+/* ---- shell record ----------------------------------------------------------
+ * One shell about one centre as nb_radial_profiles (below) reports it.  64 bytes, no padding.  w = m > 0 ? m : 0; r, v_r, u and the
+ * l_z term are defined there. */
+typedef struct nb_shell {
+    uint64_t count;         /* offset   0  bodies in the shell, massless ones included */
+    double   mass;          /* offset   8  sum w */
+    double   mr;            /* offset  16  sum w r */
+    double   mr2;           /* offset  24  sum w r^2 */
+    double   mvr;           /* offset  32  sum w v_r */
+    double   mvr2;          /* offset  40  sum w v_r^2 */
+    double   mv2;           /* offset  48  sum w |u|^2 */
+    double   mlz;           /* offset  56  sum w (dx u_y - dy u_x) */
+} nb_shell;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_shell) == 64, "nb_shell is 64 bytes");
+static_assert(offsetof(nb_shell, mass) == 8 && offsetof(nb_shell, mr) == 16 && offsetof(nb_shell, mr2) == 24 && offsetof(nb_shell, mvr) == 32 &&
+              offsetof(nb_shell, mvr2) == 40 && offsetof(nb_shell, mv2) == 48 && offsetof(nb_shell, mlz) == 56,
+              "nb_shell field offsets");
+#else
+_Static_assert(sizeof(nb_shell) == 64, "nb_shell is 64 bytes");
+_Static_assert(offsetof(nb_shell, mass) == 8 && offsetof(nb_shell, mr) == 16 && offsetof(nb_shell, mr2) == 24 && offsetof(nb_shell, mvr) == 32 &&
+               offsetof(nb_shell, mvr2) == 40 && offsetof(nb_shell, mv2) == 48 && offsetof(nb_shell, mlz) == 56,
+               "nb_shell field offsets");
+#endif
+
 /* ---- group energy record --------------------------------------------------
  * One friends-of-friends group as nb_group_binding (below) reports it: row r describes the group of row r of nb_group_catalog.
  * 32 bytes, no padding. */
@@ -919,6 +945,79 @@ int nb_group_binding(nb_sim *s, float radius, uint32_t min_members, double *phi,
  * With nb_profile_enable the count kernel is bracketed like a force launch and counts as one (nb_profile_read). */
 #define NB_PAIR_BINS_MAX 64
 int nb_pair_counts(nb_sim *s, const float *edges, uint32_t nbins, uint64_t *counts);
+
+/* Radial profiles: for each of ncenters POINTS, per shell about it, how many bodies there are and the fp64 sums of mass and velocity
+ * moments, reduced on the device.  It is what a caller does with a group once nb_group_catalog has said where it is and
+ * nb_group_binding which body is its centre: the surface or volume density profile, the enclosed mass and the half-mass radius, the
+ * radial and tangential velocity dispersion, the rotation curve (INTEGRATION.md has the recipe).  Without it a caller nb_syncs 64 B per
+ * body and runs a numpy pass per centre.
+ * INPUTS: centers holds ncenters rows of dims floats, (x, y), or (x, y, z) on a dims = 3 handle: nb_sync_positions' stride.  vcenters
+ * holds the same shape in doubles; NULL means all zero.  edges holds nbins + 1 floats, 1 <= nbins <= NB_PROFILE_BINS_MAX.
+ * out[c * nbins + b] is shell b of centre c; every one of the ncenters * nbins records is written, an empty shell is all zero.
+ * SHELLS AND DISTANCE: nb_pair_counts' rule word for word.  e2[t] = edges[t] * edges[t], one fp32 multiply on the host; shell b holds
+ * the bodies with e2[b] <= d2 < e2[b + 1]: closed below, open above.  d2 is fp32, one rounding per operation, no contraction:
+ *     dx = x_j - c_x      dy = y_j - c_y      d2 = dx * dx + dy * dy
+ * and on a dims = 3 handle dz = z_j - c_z, d2 = (dx * dx + dy * dy) + dz * dz: a profile wants the 3-D radius (nb_group_binding also
+ * lets z into its distance).  A centre is a point, not a body: there is no self term.  A body that lies on a centre is in shell 0
+ * when edges[0] == 0 and in no shell otherwise.  A body with a non-finite coordinate is in no shell; so is a d2 that overflows to
+ * +inf.  count is exact.
+ * MOMENTS, all fp64, one rounding per operation, no contraction.  A body's values are the float values nb_sync returns for it,
+ * widened to double (an NB_FP64 handle's values are rounded to float first: the catalogue's rule); w = m > 0 ? m : 0;
+ *     X = (double)x_j - (double)c_x, Y, Z likewise      r2 = (X X + Y Y) + Z Z      r = sqrt(r2)
+ *     u = (double)v_j - vcenter      v_r = ((X u_x + Y u_y) + Z u_z) / r      |u|^2 = (u_x u_x + u_y u_y) + u_z u_z
+ * and a body adds 1 to count, w to mass, w r to mr, w r2 to mr2, w v_r to mvr, (w v_r) v_r to mvr2, w |u|^2 to mv2 and
+ * w (X u_y - Y u_x) to mlz: the z component of the angular momentum on either kind of handle (the Z terms are absent in 2-D).  Where
+ * r == 0 the body adds to count, mass and mv2 only; its other terms are +0.  A massless, negative-mass or NaN-mass body is counted
+ * and weighs nothing.  A shell that holds a body with a non-finite mass or velocity gets what the arithmetic gives.
+ * ORDER: every sum is taken in an order that is a function of the bodies, the centres and the edges alone, and there is no
+ * floating-point atomic anywhere.  The bodies are sorted by the cell of a grid of cell size edges[nbins] x (1 + 2^-16) with a stable
+ * sort, (cell key, body index) ascending; a centre's CANDIDATES are the bodies of the 3 x 3 cells round its own cell, the cell row below
+ * first, each row in sorted order.  The candidates are cut into pieces of 1024.  Inside a piece a shell's sum starts at +0 and takes
+ * the terms of its bodies from left to right in candidate order.  A centre with at most 1024 candidates is one piece.  Otherwise
+ * the pieces k = 0 .. K - 1 are added so: S_s = piece s + piece (s + 32) + piece (s + 64) + ..., left to right, for s = 0 .. 31 (+0
+ * where s >= K), then S_s += S_(s + h) for h = 16, 8, 4, 2, 1, and the sum is S_0 (tests/radial_profiles_model.py states the contract,
+ * not this order).  CONSEQUENCES: two handles, and two calls on one handle, agree byte for byte; permuting the bodies leaves every
+ * count unchanged and changes the doubles through the order of summation only; permuting the centres permutes the rows of out byte
+ * for byte, and a centre's row does not depend on the other centres of the call.
+ * WHICH BODIES: all n bodies of the CURRENT replica, at the positions of all work enqueued so far: nb_neighbors' rules.  Every kind
+ * of handle nb_group_catalog serves: fp32 and fp64, dims 2 and 3, direct and tree with any flags, all-reduce and single-rank sharded
+ * handles.  NB_ESTATE, with the catalogue's message, on a handle with nb_owned_count(s) < n: a block handle holds only its block's
+ * velocities.
+ * ERRORS: NB_EINVAL, naming the argument and the offending index, before any device work, in this order: a NULL handle, centers,
+ * edges or out; ncenters outside 1 .. 1 048 576; nbins outside 1 .. 64; ncenters * nbins > 1 048 576 (64 MiB of records: the cap is a
+ * condition, not a measurement; it keeps the device plane and the staging buffer bounded); nb_pair_counts' edge rules word for word
+ * (finite, edges[0] >= 0, strictly ascending, squares strictly ascending in float, r2max finite and not 0); a non-finite centre
+ * coordinate; a non-finite vcenters value.  NB_ESTATE while a split step is in flight.  The call synchronises; a pending once-only
+ * report leaves through it as through nb_neighbors (NB_ENOMEM, once), and nothing is written then.  NB_ENOMEM if the centres see
+ * more than 2^31 - 1 pieces of candidates between them.
+ * Nothing of the handle changes: positions, velocities, acc[], frame counter, tree arrays and nb_tree_stats are untouched, and the
+ * next step is bit-identical to one on a handle that never called this.  It may alternate with nb_neighbors, nb_groups,
+ * nb_group_catalog, nb_group_binding and nb_pair_counts on one handle at any radii.
+ * out may be any host memory: ranges known to be page-locked (nb_host_alloc / nb_host_register) are written by the copy engine
+ * directly, anything else moves through the query calls' shared staging buffer.
+ * Memory: nothing until the first call; then (growth only, freed by nb_destroy) nb_neighbors' 40 bytes per body of the replica and its
+ * sort storage, if that call has not made them yet; 84 bytes per centre of the largest call seen (the centre 12, its velocity 24,
+ * its three cell ranges 24, two piece counts 8 and their prefix sums 16) and the scans' temporary storage; 64 bytes per record of
+ * the largest ncenters * nbins seen, at most 64 MiB, and as much page-locked staging once a destination needs it; and 64 bytes x nbins
+ * per PIECE OF A CENTRE THAT IS SPLIT, which no cap bounds: a centre whose last edge covers all n bodies takes n / 1024 rows of nbins
+ * records (8 MiB at 8 388 608 bodies and 16 shells), and m such centres take m times that.  The caller chooses the edges.
+ * Cost: the cell sort of nb_pair_counts, one small launch that finds every centre's ranges, two prefix sums over the centres, one
+ * read-back of their totals, then the sweep: ONE WAVE PER PIECE, so one centre that covers the system is n / 1024 waves all over the
+ * chip and 65 536 small centres are 65 536 single waves; a second launch adds the rows of the split centres.  The cost of the sweep
+ * is proportional to the candidates, the bodies in the 3 x 3 cells round each centre.  On an MI355X, Plummer spheres, 16 shells, records
+ * into nb_host_alloc memory (profiles/radial_profiles_bench.log; DESIGN.md section 6, "Radial profiles"): ONE centre at the origin whose
+ * last edge lies beyond the whole sphere, at 262 144 / 1 048 576 / 8 388 608 (tree handle) bodies 0.22 / 0.32 / 1.14 ms, of which the
+ * sweep 0.06 / 0.09 / 0.31 ms, where nb_raster's call on the same handle takes 0.52 / 0.64 / 1.57 ms and the host route (nb_sync, numpy
+ * histograms with weights, one thread) 43 / 170 / 1 430 ms; into a pageable array the same within 0.01 ms.  65 536 centres, the most
+ * bound bodies of nb_group_binding's groups at 1 048 576 bodies and a mean of 1 link per body, last edge 4 linking lengths: 2.01 ms,
+ * of which the sweep 0.12 ms and most of the rest the 64 MiB of records (4.55 ms into a pageable array), where the host route (nb_sync,
+ * scipy's cKDTree, numpy per centre) takes 1 685 ms.  16 384 bodies in ONE cell: one centre 0.15 ms (sweep 0.06 ms: 16 waves do not
+ * fill the chip); every body a centre 4.96 ms, 6.0e10 body-centre tests per second (256 MiB of partial rows).  The other form of the
+ * per-shell sum, a masked wave reduction per occupied shell, has not been written.
+ * With nb_profile_enable the sweep (with its second launch) is bracketed like a force launch and counts as one (nb_profile_read). */
+#define NB_PROFILE_BINS_MAX 64
+int nb_radial_profiles(nb_sim *s, const float *centers, const double *vcenters, size_t ncenters, const float *edges, uint32_t nbins,
+                       nb_shell *out);
 
 /* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
  * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without

@@ -11,6 +11,7 @@ from ._lib import (  # noqa: F401
     BODY_DTYPE,
     GROUP_DTYPE,
     GROUP_ENERGY_DTYPE,
+    SHELL_DTYPE,
     NODE_DTYPE,
     NBodyError,
     PinnedBodies,
@@ -27,6 +28,7 @@ __all__ = [
     "BODY_DTYPE",
     "GROUP_DTYPE",
     "GROUP_ENERGY_DTYPE",
+    "SHELL_DTYPE",
     "NODE_DTYPE",
     "NBodyError",
     "PinnedBodies",

@@ -97,6 +97,17 @@ GROUP_ENERGY_DTYPE = np.dtype(
 )
 
 
+#: numpy view of the 64-byte ``nb_shell`` record of include/nbody.h, as ``nb_radial_profiles`` fills it (no padding)
+SHELL_DTYPE = np.dtype(
+    {
+        "names": ["count", "mass", "mr", "mr2", "mvr", "mvr2", "mv2", "mlz"],
+        "formats": [np.uint64] + [np.float64] * 7,
+        "offsets": [0, 8, 16, 24, 32, 40, 48, 56],
+        "itemsize": 64,
+    }
+)
+
+
 def nodes_array(n: int) -> np.ndarray:
     """Zero-initialised array of n 128-byte Node records (padding zero)."""
     return np.zeros(n * NODE_DTYPE.itemsize, dtype=np.uint8).view(NODE_DTYPE)
@@ -240,6 +251,7 @@ PROTOTYPES = {
     "nb_group_catalog": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nb_group_binding": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nb_pair_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nb_radial_profiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),
     "nb_owned_begin": (C.c_size_t, [C.c_void_p]),

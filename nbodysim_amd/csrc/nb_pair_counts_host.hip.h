@@ -41,27 +41,35 @@ static void launch_pair_counts(nb_sim *s, uint32_t g, const float *e2, uint32_t 
     }, s->i_count == s->n);
 }
 
+// The edge rules nb_pair_counts and nb_radial_profiles share, behind the check of nbins: finite, edges[0] >= 0, strictly ascending, squares
+// strictly ascending in float, r2max finite and not 0.  e2[0 .. nbins] receives the squares.
+static int pair_counts_edges(const char *name, const float *edges, uint32_t nbins, float *e2)
+{
+    for (uint32_t t = 0; t <= nbins; ++t)
+        if (!std::isfinite(edges[t])) return nb_fail(NB_EINVAL, "%s: edges[%u] is not finite (%g)", name, t, (double)edges[t]);
+    if (edges[0] < 0.0f) return nb_fail(NB_EINVAL, "%s: edges[0] must be >= 0 (got %g)", name, (double)edges[0]);
+    for (uint32_t t = 0; t < nbins; ++t)
+        if (!(edges[t] < edges[t + 1]))
+            return nb_fail(NB_EINVAL, "%s: edges must be strictly ascending (edges[%u] = %g, edges[%u] = %g)", name, t, (double)edges[t], t + 1,
+                           (double)edges[t + 1]);
+    for (uint32_t t = 0; t <= nbins; ++t) e2[t] = edges[t] * edges[t];      // one fp32 rounding: the kernel's operands
+    for (uint32_t t = 0; t < nbins; ++t)
+        if (!(e2[t] < e2[t + 1]))
+            return nb_fail(NB_EINVAL, "%s: the squares of edges[%u] = %g and edges[%u] = %g are not ascending in float (%g, %g): the bin "
+                                      "between them would be empty or inverted", name, t, (double)edges[t], t + 1, (double)edges[t + 1], (double)e2[t], (double)e2[t + 1]);
+    // r2max finite and not 0: the same fp32 product as e2[nbins], which it overwrites with itself
+    { const int rc = check_radius(name, edges[nbins], &e2[nbins]); if (rc) return rc; }
+    return NB_OK;
+}
+
 // The histogram of pair separations, DD(r): what a two-point correlation function, a radial distribution function or a correlation
 // dimension is made of, without neighbour rows capped at k or a copy of all bodies and a tree pass on the host.
 extern "C" int nb_pair_counts(nb_sim *s, const float *edges, uint32_t nbins, uint64_t *counts)
 {
     if (!s || !edges || !counts) return nb_fail(NB_EINVAL, "nb_pair_counts: NULL %s", !s ? "handle" : !edges ? "edges" : "counts");
     if (nbins < 1 || nbins > NB_PAIR_BINS_MAX) return nb_fail(NB_EINVAL, "nb_pair_counts: nbins must be 1 .. %d (got %u)", NB_PAIR_BINS_MAX, nbins);
-    for (uint32_t t = 0; t <= nbins; ++t)
-        if (!std::isfinite(edges[t])) return nb_fail(NB_EINVAL, "nb_pair_counts: edges[%u] is not finite (%g)", t, (double)edges[t]);
-    if (edges[0] < 0.0f) return nb_fail(NB_EINVAL, "nb_pair_counts: edges[0] must be >= 0 (got %g)", (double)edges[0]);
-    for (uint32_t t = 0; t < nbins; ++t)
-        if (!(edges[t] < edges[t + 1]))
-            return nb_fail(NB_EINVAL, "nb_pair_counts: edges must be strictly ascending (edges[%u] = %g, edges[%u] = %g)", t, (double)edges[t], t + 1,
-                           (double)edges[t + 1]);
     float e2[PAIR_COUNTS_WORDS];
-    for (uint32_t t = 0; t <= nbins; ++t) e2[t] = edges[t] * edges[t];      // one fp32 rounding: the kernel's operands
-    for (uint32_t t = 0; t < nbins; ++t)
-        if (!(e2[t] < e2[t + 1]))
-            return nb_fail(NB_EINVAL, "nb_pair_counts: the squares of edges[%u] = %g and edges[%u] = %g are not ascending in float (%g, %g): the bin "
-                                      "between them would be empty or inverted", t, (double)edges[t], t + 1, (double)edges[t + 1], (double)e2[t], (double)e2[t + 1]);
-    // r2max finite and not 0: the same fp32 product as e2[nbins], which it overwrites with itself
-    { const int rc = check_radius("nb_pair_counts", edges[nbins], &e2[nbins]); if (rc) return rc; }
+    { const int rc = pair_counts_edges("nb_pair_counts", edges, nbins, e2); if (rc) return rc; }
     { const int rc = query_enter(s, "nb_pair_counts"); if (rc) return rc; }     // no snapshot wait, as in nb_neighbors
     const uint32_t n = (uint32_t)s->n, blocks = (n + BLOCK - 1) / BLOCK;
     // workgroups that stay: a workgroup reduces its lanes' counters once, behind its last batch

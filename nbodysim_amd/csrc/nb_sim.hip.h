@@ -17,6 +17,7 @@
 #include "nb_group_catalog.hip.h"
 #include "nb_group_binding.hip.h"
 #include "nb_pair_counts.hip.h"
+#include "nb_profiles.hip.h"
 #include "nb_order.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -296,6 +297,23 @@ struct nb_sim {
         uint64_t *words = nullptr;             // device: the 65 cumulative counters, the rows added up
         uint64_t *host = nullptr;              // page-locked mirror of them
     } pairs;
+
+    // nb_radial_profiles (nb_profiles.hip.h): nothing in `prf` exists before the first call; the cells and the sort are `nbr`'s
+    struct Profiles {
+        uint64_t cap = 0;                      // entries the seven per-centre arrays hold: ncenters + 1 of the largest call seen
+        ProfileCentre *cen = nullptr;          // the centres as passed, `dims` floats each, packed
+        ProfileVelocity *vcen = nullptr;       // their velocities, `dims` doubles each, packed
+        ProfileRanges *rng = nullptr;          // the three key ranges of a centre
+        uint32_t *pieces = nullptr, *split = nullptr;   // pieces of a centre; the same where it is more than one, else 0
+        uint64_t *first = nullptr, *prow = nullptr;     // their exclusive scans: a centre's first piece, its first partial row
+        void *tmp = nullptr;                   // rocprim temporary storage of the scans (asked for cap elements)
+        size_t tmp_bytes = 0;
+        uint64_t out_cap = 0;                  // records `out` holds: the largest ncenters x nbins seen
+        nb_shell *out = nullptr;
+        uint64_t part_cap = 0;                 // records `partial` holds: nbins per piece of the split centres of the largest call seen
+        nb_shell *partial = nullptr;
+        uint64_t *host = nullptr;              // page-locked: the two totals
+    } prf;
 
     // body order of the whole-system symmetric path (nb_order.hip.h): nothing in `ord` is allocated unless `on`
     struct Order {

@@ -263,6 +263,13 @@ public:
     {
         check(nb_pair_counts(sim_, edges, nbins, counts), "nb_pair_counts");
     }
+    // Shell sums about `ncenters` points (nb_radial_profiles, include/nbody.h), at the positions of the work enqueued so far:
+    // out[c * nbins + b] is the count and the fp64 mass and velocity moments of the bodies with edges[b] <= |x - centre c| < edges[b + 1]
+    // (squares compared in float).  centers holds `dims` floats a centre, vcenters (may be null: zero) as many doubles.
+    void radial_profiles(const float *centers, const double *vcenters, size_t ncenters, const float *edges, uint32_t nbins, nb_shell *out)
+    {
+        check(nb_radial_profiles(sim_, centers, vcenters, ncenters, edges, nbins, out), "nb_radial_profiles");
+    }
     nb_sim *handle() { return sim_; }
 
 private:

@@ -415,6 +415,37 @@ class Simulation:
         L.check("nb_pair_counts", self._lib.nb_pair_counts(self._h, e.ctypes.data, e.size - 1, counts.ctypes.data), self._lib)
         return counts
 
+    def radial_profiles(self, centers, edges, vcenters=None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Shell sums about many centres, reduced on the device (``nb_radial_profiles``; synchronises).  ``centers`` is
+        ``(ncenters, dims)``, passed on as float32; ``edges`` the ``nbins + 1`` strictly ascending shell edges, 1 <= nbins <= 64, passed
+        on as float32; ``vcenters`` the centres' velocities, ``(ncenters, dims)``, passed on as float64 (default: zero).  Returns a
+        ``(ncenters, nbins)`` ``SHELL_DTYPE`` array: ``count`` and the fp64 sums ``mass``, ``mr``, ``mr2``, ``mvr``, ``mvr2``, ``mv2``,
+        ``mlz`` of the bodies with ``edges[b]**2 <= d2 < edges[b+1]**2`` about centre c, d2 in fp32 (3-D on a ``dims = 3`` handle).
+        ``out``: a writeable C-contiguous ``SHELL_DTYPE`` array of that shape (one over ``nb_host_alloc`` memory is written by the copy
+        engine directly); default a new array.  The handle must own all n bodies.  The arguments are validated by the library
+        (include/nbody.h has the rules)."""
+        dims = 3 if self._params.dims == 3 else 2
+        c = np.ascontiguousarray(centers, dtype=np.float32)
+        if c.ndim != 2 or c.shape[1] != dims:
+            raise ValueError(f"radial_profiles: centers must be (ncenters, {dims}) (got shape {c.shape})")
+        e = np.ascontiguousarray(edges, dtype=np.float32)
+        if e.ndim != 1 or e.size < 2:
+            raise ValueError("radial_profiles: edges must be a 1-D sequence of at least two values")
+        v = None
+        if vcenters is not None:
+            v = np.ascontiguousarray(vcenters, dtype=np.float64)
+            if v.shape != c.shape:
+                raise ValueError(f"radial_profiles: vcenters must have the shape of centers, {c.shape} (got {v.shape})")
+        shape = (c.shape[0], e.size - 1)
+        if out is None:
+            out = np.zeros(shape, dtype=L.SHELL_DTYPE)
+        elif (not isinstance(out, np.ndarray) or out.dtype != L.SHELL_DTYPE or out.shape != shape or not out.flags.c_contiguous
+              or not out.flags.writeable):
+            raise TypeError(f"out must be a writeable C-contiguous {shape} numpy array of nbodysim_amd.SHELL_DTYPE (64-byte nb_shell records)")
+        L.check("nb_radial_profiles", self._lib.nb_radial_profiles(self._h, c.ctypes.data, None if v is None else v.ctypes.data, c.shape[0],
+                                                                   e.ctypes.data, e.size - 1, out.ctypes.data), self._lib)
+        return out
+
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
         L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)
