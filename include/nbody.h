@@ -1019,6 +1019,65 @@ int nb_pair_counts(nb_sim *s, const float *edges, uint32_t nbins, uint64_t *coun
 int nb_radial_profiles(nb_sim *s, const float *centers, const double *vcenters, size_t ncenters, const float *edges, uint32_t nbins,
                        nb_shell *out);
 
+/* The field at arbitrary POINTS: potential and acceleration where the caller asks, not only at the bodies (nb_potentials,
+ * nb_accelerations).  With d = x_j - p:
+ *     phi(p) = - sum_j m_j / sqrt(|d|^2 + eps^2)        acc(p) = sum_j m_j d / (|d|^2 + eps^2)^(3/2)        (G = 1, the handle's eps)
+ * It is the potential or acceleration map under nb_raster's view, the circular velocity v_c^2 = r |a_r| beside nb_radial_profiles'
+ * shells, the tidal field across a group of nb_group_catalog, the force on a probe before it is spawned (INTEGRATION.md has recipes).
+ * Without it a caller adds massless tracer bodies and creates the handle again (another n, plan, root cell and set of indices), or
+ * nb_syncs 64 B per body and sums on the host.
+ * INPUTS: points holds npoints rows of dims floats, (x, y), or (x, y, z) on a dims = 3 handle: nb_sync_positions' stride and
+ * nb_radial_profiles' centers.  phi receives npoints doubles, acc npoints x dims doubles.  Either of phi / acc may be NULL, not
+ * both; a plane that is not asked for is neither computed, written nor copied, and the bits of one plane do not depend on whether
+ * the other was asked for.
+ * WHICH BODIES: all n bodies of the CURRENT replica at the positions of all work enqueued so far: nb_potentials' rules (on a
+ * sharded handle the replica must be complete).  Every kind of handle: fp32 and fp64, dims 2 and 3, either integrator, sharded or
+ * not, direct or tree with any flags.
+ * A POINT IS NOT A BODY: there is no self term and no mask by index.  A point that lies on a body takes -m_j / eps into phi and
+ * nothing into acc (d = 0).  With eps = 0 a pair whose r^2, in the arithmetic of the sweep, is exactly 0 adds nothing to either
+ * output, and the result stays finite.
+ * ARITHMETIC of the direct sweep (every handle but a NB_FLAG_TREE_ENERGY one: nb_potentials' split).  NB_FP32: per pair a float
+ * displacement, r^2 by fused multiply-adds onto eps^2, inv = v_rsq_f32(r^2), then phi += m_j inv and, with s = m_j ((inv inv) inv),
+ * a_c += d_c s, each a fused multiply-add in fp32 over runs of 64 consecutive j (a run starts at every multiple of 64 from j = 0),
+ * the runs added in fp64, the result fp64.  phi is nb_potentials' arithmetic word for word: within 4e-6 relative of the fp64 sum,
+ * and, with eps > 0, phi at the position of a massless body has the bits of that body's nb_potentials value.  Each component of
+ * acc is within 4.2e-6 of S_c = sum_j |term_j| of that component (6.5 ulp per term and the 63 roundings of a run;
+ * tests/field_model.py is the numpy statement): the bound is on the cancellation-free scale, not on |a|.  NB_FP64: the float points
+ * widened, fp64 throughout, the terms added in j order (1.4e-16 per reciprocal square root).
+ * DETERMINISM: a point's row depends on the bodies, eps, the precision and that point only: not on npoints, on the launch
+ * geometry or on the other points.  Two handles agree bit for bit, and permuting the points permutes the rows byte for byte.
+ * NB_FLAG_TREE_ENERGY handles: the tree build of nb_energy and the leaf residual run, then one per-lane walker per point.  A point
+ * walks exactly as a massless body at that position walks: nb_potentials' float64 terms for phi (quadrupole and leaf residual
+ * included) and, in the same loop, the float32 terms of the force walk for acc with the handle's own rsqrt_mode, widened on
+ * store: phi has the bits nb_potentials gives a massless body there, and acc those nb_accelerations gives it.  A leaf exactly under
+ * the point gives no term (d^2 = 0): the one difference from the direct sweep.  NB_FLAG_TREE_RELATIVE is not applied (a point has
+ * no previous acceleration): the walk is the theta walk.  The points are walked in caller order, 64 consecutive points to a wave:
+ * a row-major image is coherent enough for the per-lane walk; sorting the points and a wave-uniform group walk have not been
+ * written.  As for nb_potentials the tree arrays are rebuilt, nb_tree_stats describes this build, and a failed build makes THIS
+ * call return NB_ENOMEM through the once-only report, with nothing written.
+ * Nothing else of the handle changes: positions, velocities, acc[] and the frame counter are untouched, and the next step is
+ * bit-identical to one on a handle that never called this.
+ * ERRORS: NB_EINVAL before any device work, in this order: a NULL handle; NULL points; phi and acc both NULL; npoints outside
+ * 1 .. NB_FIELD_POINTS_MAX (the cap is a condition that bounds the scratch, not a measurement); the first non-finite coordinate,
+ * named by index and axis.  NB_ESTATE while a split step is in flight.  The call synchronises; a pending once-only report leaves
+ * through it as through nb_radial_profiles (NB_ENOMEM, once), and nothing is written then.  phi and acc may be any host memory:
+ * ranges known to be page-locked (nb_host_alloc / nb_host_register) are written by the copy engine directly, anything else moves
+ * through the query calls' shared staging buffer.
+ * Memory: nothing until the first call; then (growth only, freed by nb_destroy) 4 dims + 8 (dims + 1) bytes per point of the largest
+ * call seen (128 MiB at the cap in 2-D), and as much page-locked staging as the larger plane once a destination needs it.
+ * Cost: npoints x n pairs on the direct sweep.  On an MI355X, fp32 2-D Plummer spheres, as many points as bodies, 262 144 / 1 048 576
+ * (profiles/field_bench.log; DESIGN.md section 6, "Field at points"): the sweep alone, phi 9.93 / 140.2 ms, acc 14.67 / 204.6 ms, both
+ * 15.80 / 222.4 ms, where on the same handle nb_potentials' sweep takes 9.92 / 139.9 ms and a one-sided force launch 11.17 / 179.7 ms:
+ * the joint sweep takes less than those two together, the acc plane alone more than the force launch (general masses, and an fp64
+ * add per output per run of 64).  The whole call, both planes, into a pageable array 16.41 / 224.1 ms, into nb_host_alloc memory
+ * 16.08 / 223.4 ms.  NB_FLAG_TREE_ENERGY handles at theta = 0.5, a 1024 x 1024 row-major grid over the half-mass square, both planes
+ * into a pageable array, at 1 048 576 / 8 388 608 bodies: 5.02 / 13.59 ms, of which the walk kernel 2.02 / 4.07 ms; the same points
+ * shuffled: 8.46 / 19.43 ms, walk 5.48 / 9.94 ms.
+ * With nb_profile_enable the sweep (the walk kernel on a NB_FLAG_TREE_ENERGY handle) is bracketed like a force launch and counts as
+ * one (nb_profile_read). */
+#define NB_FIELD_POINTS_MAX 4194304
+int nb_field(nb_sim *s, const float *points, size_t npoints, double *phi, double *acc);
+
 /* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
  * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without
  * the flag.  At creation alpha is 0.005: GADGET-2's customary ErrTolForceAcc, not a number measured for this library.  A setter

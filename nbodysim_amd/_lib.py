@@ -40,6 +40,7 @@ NB_FLAG_TREE_RELATIVE = 32768        # with NB_FORCE_TREE and NB_FLAG_TREE_LEAVE
 NB_FLAG_BODY_ORDER = 131072          # the Morton body order of the symmetric kernel at any size (default: 131 072 .. 262 144 bodies; 65536 is unassigned)
 NB_FLAG_NO_BODY_ORDER = 262144       # never: the caller's order
 NB_NO_NEIGHBOR = 0xFFFFFFFF         # the index that pads a row of nb_neighbors
+NB_FIELD_POINTS_MAX = 4194304       # the most points one nb_field call takes
 
 #: numpy view of the reference's 64-byte ``Body`` record (Body.hpp:6-13, Vec2.hpp:17-20)
 BODY_DTYPE = np.dtype(
@@ -252,6 +253,7 @@ PROTOTYPES = {
     "nb_group_binding": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nb_pair_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "nb_radial_profiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nb_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),
     "nb_owned_begin": (C.c_size_t, [C.c_void_p]),
@@ -351,10 +353,24 @@ def default_params() -> nb_params:
     return p
 
 
+class BodyArray(np.ndarray):
+    """Body records whose ``copy()`` keeps every byte of a record.  numpy copies a record array field by field and leaves the bytes
+    between the fields of the new array unset, and the z of a 3-D body (``BODY3_DTYPE``) lies between the fields of
+    ``BODY_DTYPE``: a plain copy of ``plummer_3d(n)`` would lose it."""
+
+    def copy(self, order="C"):
+        if self.dtype.names is None or self.ndim != 1:
+            return super().copy(order)
+        raw = f"V{self.dtype.itemsize}"
+        out = np.empty(self.shape[0] * self.dtype.itemsize, dtype=np.uint8).view(self.dtype).view(type(self))
+        out.view(raw)[...] = self.view(raw)
+        return out
+
+
 def bodies_array(n: int) -> np.ndarray:
     """Zero-initialised array of n 64-byte Body records (padding zero)."""
     raw = np.zeros(n * BODY_DTYPE.itemsize, dtype=np.uint8)
-    return raw.view(BODY_DTYPE)
+    return raw.view(BODY_DTYPE).view(BodyArray)
 
 
 class PinnedBodies:

@@ -573,7 +573,7 @@ static int fence_foreign_work(nb_sim *s)
 }
 
 // ---- what the query calls (nb_tree_nodes, nb_raster, nb_potentials, nb_neighbors, nb_groups, nb_group_catalog, nb_group_binding, nb_pair_counts,
-// nb_radial_profiles) share ----
+// nb_radial_profiles, nb_field) share ----
 static int snapshot_wait(nb_sim *s);
 
 // The opening of a query call, behind its argument checks: no split step in flight, the device bound, (nb_potentials: the staging
@@ -619,6 +619,7 @@ static int copy_plane(nb_sim *s, void *dst, const void *src, size_t bytes) { ret
 #include "nb_group_binding_host.hip.h"
 #include "nb_pair_counts_host.hip.h"
 #include "nb_profiles_host.hip.h"
+#include "nb_field_host.hip.h"
 #include "nb_order_host.hip.h"
 
 // what every synchronising call reports once: a collision step over capacity, a failed tree build

@@ -1,8 +1,8 @@
 // nb_sim.hip.h — the handle behind the C ABI, and what every piece of host code around it needs: the HIP error check, the
 // device binding, the dispatchers from run-time choices to template arguments.  Included by nb_capi.hip (the one device
 // translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h, nb_raster_host.hip.h,
-// nb_potential_host.hip.h, nb_neighbors_host.hip.h, nb_groups_host.hip.h, nb_group_catalog_host.hip.h, nb_group_binding_host.hip.h, nb_pair_counts_host.hip.h and
-// nb_order_host.hip.h.
+// nb_potential_host.hip.h, nb_neighbors_host.hip.h, nb_groups_host.hip.h, nb_group_catalog_host.hip.h, nb_group_binding_host.hip.h, nb_pair_counts_host.hip.h,
+// nb_profiles_host.hip.h, nb_field_host.hip.h and nb_order_host.hip.h.
 #pragma once
 #include "nbody.h"
 #include "nbody_debug.h"
@@ -18,6 +18,7 @@
 #include "nb_group_binding.hip.h"
 #include "nb_pair_counts.hip.h"
 #include "nb_profiles.hip.h"
+#include "nb_field.hip.h"
 #include "nb_order.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -314,6 +315,12 @@ struct nb_sim {
         nb_shell *partial = nullptr;
         uint64_t *host = nullptr;              // page-locked: the two totals
     } prf;
+
+    // nb_field (nb_field.hip.h): nothing in `fld` exists before the first call; one block, grown by the largest npoints seen
+    struct Field {
+        uint64_t bytes = 0;                    // bytes `buf` holds: 8 (dims + 1) + 4 dims per point
+        void *buf = nullptr;                   // the call's phi plane, then its acc plane, then its points
+    } fld;
 
     // body order of the whole-system symmetric path (nb_order.hip.h): nothing in `ord` is allocated unless `on`
     struct Order {

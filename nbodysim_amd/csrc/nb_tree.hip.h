@@ -744,6 +744,59 @@ void tree_potential_alone(const float4 *__restrict__ nd, const uint32_t *__restr
     if constexpr (!EMIT) tree_energy_reduce(k, u, ksum, usum);
 }
 
+// nb_field on a NB_FLAG_TREE_ENERGY handle: one per-lane walker per caller-given POINT, in caller order.  A point walks exactly as a
+// massless body at that position walks: the loop above (EMIT, the theta test) with its float64 terms for phi, and in the same loop the
+// float32 terms of tree_walk_one<RSQ, true, QUAD> for acc, the running float32 sums widened on store.  A leaf exactly under the point
+// gives no term (d^2 = 0).  The relative test is not applied: a point has no previous acceleration.  PHI / ACC pick the planes; the
+// nodes visited and every operation of a plane are the same whichever are computed.
+template <int RSQ, bool QUAD, bool PHI, bool ACC>
+__global__ __launch_bounds__(256)
+void tree_field_walk(const float4 *__restrict__ nd, const uint32_t *__restrict__ nx, const float2 *__restrict__ points, uint32_t npoints,
+                     float eps2f, double eps2, float theta2, const TreeStats *__restrict__ st, const float *__restrict__ lo,
+                     const float4 *__restrict__ qm, double *__restrict__ phi_out, double2 *__restrict__ acc_out)
+{
+    static_assert(PHI || ACC, "a plane must be asked for");
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npoints || st->fail) return;
+    const float2 p = points[i];
+    const uint32_t total = (uint32_t)st->nodes;
+    double phi = 0.0;
+    float sx = 0.f, sy = 0.f;
+    uint32_t node = 0;
+    while (node < total) {
+        const float4 q = nd[node];
+        const uint32_t next = nx[node];
+        float dx, dy, d2;
+        bool far;
+        {
+#pragma clang fp contract(off)
+            dx = q.x - p.x; dy = q.y - p.y;
+            d2 = dx * dx + dy * dy;
+            far = q.w < d2 * theta2;
+        }
+        const bool leaf = next == node + 1u;
+        auto mono = [&]() {
+            if constexpr (ACC) tree_mono_term<RSQ>(q.z, dx, dy, d2, eps2f, sx, sy);
+            if constexpr (PHI) phi += tree_potential_mono(q, tree_potential_mass(q, leaf, node, lo), p, eps2);
+        };
+        if (far) {
+            if (d2 > 0.f) {
+                if (QUAD && !leaf) {
+                    const float4 m = qm[node];
+                    if constexpr (ACC) tree_quad_term<RSQ>(q, m, dx, dy, d2, eps2f, sx, sy);
+                    if constexpr (PHI) phi += tree_potential_quad(q, m, p, eps2);
+                } else mono();
+            }
+            node = next > node ? next : node + 1u;
+        } else {
+            if (leaf && q.z != 0.f && d2 > 0.f) mono();
+            node = node + 1u;
+        }
+    }
+    if constexpr (PHI) phi_out[i] = phi;
+    if constexpr (ACC) acc_out[i] = make_double2((double)sx, (double)sy);
+}
+
 // the windows: tree_walk_group's loop (node index through readfirstlane, one ballot, the moment record loaded inside the
 // wave-uniform accepted-branch path).  The lanes that take no part stay out of the loop, so they neither vote nor lead, and
 // join the block reduction with zeros.

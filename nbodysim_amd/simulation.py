@@ -446,6 +446,35 @@ class Simulation:
                                                                    e.ctypes.data, e.size - 1, out.ctypes.data), self._lib)
         return out
 
+    def field(self, points, phi: bool = True, acc: bool = True, out=None):
+        """Potential and acceleration of all n bodies at arbitrary points (``nb_field``; synchronises).  ``points`` is
+        ``(npoints, dims)``, passed on as float32.  Returns ``phi`` (float64, ``(npoints,)``), ``acc`` (float64, ``(npoints, dims)``) or
+        the pair ``(phi, acc)``, as asked for; a plane that is not asked for is not computed.  ``out``: the destination, a writeable
+        C-contiguous float64 array of that shape, or the pair of them where both planes are asked for (one over ``nb_host_alloc``
+        memory is written by the copy engine directly); default new arrays.  A point is not a body: no self term; a point on a body
+        takes ``-m / eps`` into phi and nothing into acc.  The arguments are validated by the library (include/nbody.h has the rules)."""
+        if not (phi or acc):
+            raise ValueError("field: at least one of phi and acc must be asked for")
+        dims = 3 if self._params.dims == 3 else 2
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != dims:
+            raise ValueError(f"field: points must be (npoints, {dims}) (got shape {p.shape})")
+        want = ([("phi", (p.shape[0],))] if phi else []) + ([("acc", (p.shape[0], dims))] if acc else [])
+        if out is None:
+            planes = [np.empty(shape, dtype=np.float64) for _, shape in want]
+        else:
+            planes = list(out) if len(want) == 2 and isinstance(out, (tuple, list)) else [out]
+            if len(planes) != len(want):
+                raise TypeError("out must be a pair (phi, acc) of arrays where both planes are asked for, one array otherwise")
+            for a, (what, shape) in zip(planes, want):
+                if (not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.shape != shape or not a.flags.c_contiguous
+                        or not a.flags.writeable):
+                    raise TypeError(f"out for {what} must be a writeable C-contiguous {shape} numpy array of float64")
+        by = dict(zip((w for w, _ in want), planes))
+        L.check("nb_field", self._lib.nb_field(self._h, p.ctypes.data, p.shape[0], by["phi"].ctypes.data if phi else None,
+                                               by["acc"].ctypes.data if acc else None), self._lib)
+        return tuple(planes) if len(planes) == 2 else planes[0]
+
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
         L.check("nb_tree_alpha", self._lib.nb_tree_alpha(self._h, alpha), self._lib)
