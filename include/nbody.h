@@ -232,8 +232,8 @@ enum { NB_FORCE_DIRECT = 0,    /* every pair: the kernels this library is built 
                                   bit for bit, whatever the order of the bodies; with NB_RSQRT_EXACT the same nodes are accepted and
                                   the term uses the hardware rsqrt and FMA.  A body with mass == 0 is not inserted (it is still
                                   accelerated and integrated); positions must be finite.
-                                  Unsharded 2-D fp32 kick-drift handles only (nb_create: NB_EINVAL otherwise, naming the
-                                  combination); any rsqrt_mode, any extras.  REFUSED with it: NB_FP64, dims = 3, NB_INTEGRATOR_KDK,
+                                  Unsharded 2-D fp32 handles of the kick-drift, DKD or FR4 integrator only (nb_create: NB_EINVAL
+                                  otherwise, naming the combination); any rsqrt_mode, any extras the integrator takes.  REFUSED with it: NB_FP64, dims = 3, NB_INTEGRATOR_KDK,
                                   shard_world > 1, i_count < n, NB_FLAG_SHARD_SINGLE / _ALLREDUCE, NB_SUM_SEQUENTIAL.  IGNORED with
                                   it (they select or shape the direct-sum launches, none of which a tree handle ever runs; range
                                   checks still apply): NB_FLAG_NO_SYMMETRY, _NO_UNIFORM_MASS, _NO_GUIDED_TAIL, _MASS_SCALING,
@@ -250,7 +250,22 @@ enum { NB_FORCE_DIRECT = 0,    /* every pair: the kernels this library is built 
 
 /* integrator */
 enum { NB_INTEGRATOR_KICK_DRIFT = 0, /* Simulation.hpp:129-131,160-163 (reference) */
-       NB_INTEGRATOR_KDK = 1 };      /* kick-drift-kick leapfrog (build extension) */
+       NB_INTEGRATOR_KDK = 1,        /* kick-drift-kick leapfrog (build extension) */
+       /* Compositions of a leading drift and stages (force at the current x; v += a k h; x += v d h) — one step of size h:
+            DKD   drift 1/2;      stage (1, 1/2):  second order, time-reversible, x and v synchronised, ONE force evaluation per step
+            FR4   drift theta/2;  stages (theta, (1 - theta)/2), (1 - 2 theta, (1 - theta)/2), (theta, theta/2) with
+                  theta = 1 / (2 - 2^(1/3)): Forest-Ruth, fourth order, three force evaluations per step
+          Every coefficient * h is formed in double from the float h that nb_step resolved and rounded once to the handle's real.
+          nb_frame grows by 1 per step; acc[] is the last stage's evaluation; every step is self-contained (nb_step(1) then nb_step(3)
+          gives the bits of nb_step(4)).  Every UNSHARDED handle takes them: fp32 and fp64, dims 2 and 3, the symmetric and the
+          one-sided path, NB_SUM_SEQUENTIAL, either rsqrt mode, the Morton body order, NB_FORCE_TREE with any of its flags (where a
+          stage's build fails, that stage applies neither its kick nor its drift; the leading drift is unconditional).  nb_create
+          refuses them (NB_EINVAL, naming both parts) with shard_world > 1, i_count < n, NB_FLAG_SHARD_SINGLE, NB_FLAG_SHARD_ALLREDUCE and
+          NB_EXTRA_COLLIDE; FR4 with any extras (its middle kick runs backwards, which the clamp and the damped boundary cannot).
+          DKD applies NB_EXTRA_VCLAMP / NB_EXTRA_BOUNDARY in its one kick, at the midpoint position.  nb_step only (nb_step_begin
+          refuses them, as it refuses KDK). */
+       NB_INTEGRATOR_DKD = 2,        /* drift-kick-drift leapfrog */
+       NB_INTEGRATOR_FR4 = 3 };      /* Forest-Ruth 4th-order composition */
 
 /* nb_params.flags bit mask: algorithm switches (all 0 = the fast defaults) */
 enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered pair evaluated); a sharded

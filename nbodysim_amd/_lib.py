@@ -25,7 +25,7 @@ NB_FP32, NB_FP64 = 0, 1
 NB_RSQRT_EXACT, NB_RSQRT_QUAKE = 0, 1
 NB_SUM_TILED, NB_SUM_SEQUENTIAL = 0, 1
 NB_EXTRA_VCLAMP, NB_EXTRA_BOUNDARY, NB_EXTRA_COLLIDE = 1, 2, 4
-NB_INTEGRATOR_KICK_DRIFT, NB_INTEGRATOR_KDK = 0, 1
+NB_INTEGRATOR_KICK_DRIFT, NB_INTEGRATOR_KDK, NB_INTEGRATOR_DKD, NB_INTEGRATOR_FR4 = 0, 1, 2, 3
 NB_FORCE_DIRECT, NB_FORCE_TREE = 0, 1
 NB_POS_CURRENT, NB_POS_NEXT = 0, 1
 NB_SHARD_NONE, NB_SHARD_ALLGATHER, NB_SHARD_SYMMETRIC, NB_SHARD_ALLREDUCE = 0, 1, 2, 3

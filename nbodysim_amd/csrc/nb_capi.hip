@@ -696,6 +696,12 @@ static int do_upload(nb_sim *s, const nb_body *in)
     return NB_OK;
 }
 
+// The composed integrators (NB_INTEGRATOR_DKD, NB_INTEGRATOR_FR4: step_composed below) by name; NULL for the other two.
+static const char *composed_name(int integrator)
+{
+    return integrator == NB_INTEGRATOR_DKD ? "DKD" : integrator == NB_INTEGRATOR_FR4 ? "FR4" : nullptr;
+}
+
 extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *params)
 {
     nb_clear_error();
@@ -713,13 +719,22 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     if (p.precision != NB_FP32 && p.precision != NB_FP64) { nb_set_error("nb_create: bad precision %d", p.precision); return nullptr; }
     if (p.rsqrt_mode != NB_RSQRT_EXACT && p.rsqrt_mode != NB_RSQRT_QUAKE) { nb_set_error("nb_create: bad rsqrt_mode %d", p.rsqrt_mode); return nullptr; }
     if (p.sum_order != NB_SUM_TILED && p.sum_order != NB_SUM_SEQUENTIAL) { nb_set_error("nb_create: bad sum_order %d", p.sum_order); return nullptr; }
-    if (p.integrator != NB_INTEGRATOR_KICK_DRIFT && p.integrator != NB_INTEGRATOR_KDK) { nb_set_error("nb_create: bad integrator %d", p.integrator); return nullptr; }
+    if (p.integrator < NB_INTEGRATOR_KICK_DRIFT || p.integrator > NB_INTEGRATOR_FR4) { nb_set_error("nb_create: bad integrator %d", p.integrator); return nullptr; }
     if (p.precision == NB_FP64 && (p.rsqrt_mode == NB_RSQRT_QUAKE || p.sum_order == NB_SUM_SEQUENTIAL)) {
         nb_set_error("nb_create: quake rsqrt / sequential order are fp32 (reference arithmetic) modes");
         return nullptr;
     }
     if (p.flags & ~NB_FLAGS_KNOWN) { nb_set_error("nb_create: unknown bits in flags 0x%x", (unsigned)p.flags); return nullptr; }
     if (p.extras & ~(NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY | NB_EXTRA_COLLIDE)) { nb_set_error("nb_create: unknown bits in extras 0x%x", (unsigned)p.extras); return nullptr; }
+    if (const char *name = composed_name(p.integrator)) {
+        // the composed integrators (step_composed): whole unsharded systems, and only extras that their kicks can carry
+        const char *why = p.shard_world > 1 ? "shard_world > 1" : (p.i_count != 0 && p.i_count < n) ? "i_count < n"
+                        : (p.flags & NB_FLAG_SHARD_SINGLE) ? "NB_FLAG_SHARD_SINGLE" : (p.flags & NB_FLAG_SHARD_ALLREDUCE) ? "NB_FLAG_SHARD_ALLREDUCE"
+                        : (p.extras & NB_EXTRA_COLLIDE) ? "NB_EXTRA_COLLIDE (collisions need the kick-drift integrator)"
+                        : (p.extras && p.integrator == NB_INTEGRATOR_FR4) ? "extras (its middle kick is negative: the velocity clamp and the damped boundary "
+                                                                            "are not maps that can be run backwards)" : nullptr;
+        if (why) { nb_set_error("nb_create: the %s integrator steps whole unsharded handles; not supported with %s", name, why); return nullptr; }
+    }
     if (p.extras & NB_EXTRA_COLLIDE) {
         const char *why = p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
                         : p.shard_world > 1 ? "shard_world > 1" : (p.i_count != 0 && p.i_count < n) ? "i_count < n" : (p.flags & NB_FLAG_SHARD_SINGLE) ? "NB_FLAG_SHARD_SINGLE" : nullptr;
@@ -752,12 +767,12 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
         return nullptr;
     }
     if (p.force == NB_FORCE_TREE) {
-        const char *why = p.precision == NB_FP64 ? "NB_FP64" : p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
+        const char *why = p.precision == NB_FP64 ? "NB_FP64" : p.dims == 3 ? "dims = 3" : p.integrator == NB_INTEGRATOR_KDK ? "the KDK integrator"
                         : p.shard_world > 1 ? "shard_world > 1" : (p.i_count != 0 && p.i_count < n) ? "i_count < n"
                         : (p.flags & (NB_FLAG_SHARD_SINGLE | NB_FLAG_SHARD_ALLREDUCE)) ? "NB_FLAG_SHARD_SINGLE / NB_FLAG_SHARD_ALLREDUCE"
                         : p.sum_order != NB_SUM_TILED ? "NB_SUM_SEQUENTIAL (the walk has one order: the reference's)" : nullptr;
         if (why) {
-            nb_set_error("nb_create: the Barnes-Hut force (NB_FORCE_TREE) needs an unsharded 2-D fp32 kick-drift handle; not supported with %s", why);
+            nb_set_error("nb_create: the Barnes-Hut force (NB_FORCE_TREE) needs an unsharded 2-D fp32 kick-drift, DKD or FR4 handle; not supported with %s", why);
             return nullptr;
         }
     }
@@ -983,7 +998,7 @@ static int launch_sym_items(nb_sim *s, uint32_t first, uint32_t count, hipStream
 // One gather launch over particles [first, first + cnt): the slabs of rows [lo, hi) of every tile along the coverage lists
 // (cb, cov), plus `add` when given, stored to `dst` — or, fused, kick and drift applied in the same kernel.
 static int launch_gather(nb_sim *s, bool fuse, const uint32_t *lo, const uint32_t *hi, const uint32_t *cb, const SymCov *cov,
-                         uint32_t first, uint32_t cnt, void *dst, const void *add, double dt)
+                         uint32_t first, uint32_t cnt, void *dst, const void *add, double dt_kick, double dt_drift)
 {
     const uint32_t n = (uint32_t)s->n, per = s->dims3 ? (uint32_t)GATHER_T : (uint32_t)GATHER_P, gg = (cnt + per - 1) / per;
     const int extras = fuse ? s->p.extras : 0, kd = fuse ? INTEG_KICK | INTEG_DRIFT : 0;
@@ -993,15 +1008,15 @@ static int launch_gather(nb_sim *s, bool fuse, const uint32_t *lo, const uint32_
         const vec *ss = (const vec *)s->sym_slab_s, *sr = (const vec *)s->sym_slab_r;
         const vec *pc = fuse ? (const vec *)s->pos[s->cur] : nullptr;
         vec *pn = fuse ? (vec *)s->pos[s->cur ^ 1] : nullptr, *vel = fuse ? (vec *)s->vel : nullptr, *acc = fuse ? (vec *)s->acc : nullptr;
-        const real h = fuse ? (real)dt : (real)0;
+        const real hk = fuse ? (real)dt_kick : (real)0, hd = fuse ? (real)dt_drift : (real)0;
         with_flags([&](auto f) {
             if constexpr (L.dims3)
                 sym_gather3<real, f><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, cov, n, first, cnt, (vec *)dst, (const vec *)add,
-                                                                  pc, pn, vel, acc, h, h, kd);
+                                                                  pc, pn, vel, acc, hk, hd, kd);
             else
                 with_flags([&](auto o) {        // an ordered handle (whole system: first = 0): row k belongs to body perm[k]
                     sym_gather<real, f, o><<<gg, BLOCK, 0, s->stream>>>(ss, sr, lo, hi, cb, cov, n, first, cnt, (vec *)dst, (const vec *)add,
-                                                                        pc, pn, vel, acc, h, h, extras, kd, s->sym_sb_shift, o ? s->ord.perm : nullptr);
+                                                                        pc, pn, vel, acc, hk, hd, extras, kd, s->sym_sb_shift, o ? s->ord.perm : nullptr);
                 }, s->ord.on);
         }, fuse);
     });
@@ -1012,11 +1027,11 @@ static int launch_gather(nb_sim *s, bool fuse, const uint32_t *lo, const uint32_
 // Sum of the slabs.  fuse_step (whole-system handles): apply kick and drift in the same kernel; otherwise the
 // summed (unsharded) or partial (sharded rank) acceleration of every particle is stored: slab 0 / acc_full.
 // A sharded rank's late items are left out here (launch_sym_gather_late folds them in).
-static int launch_sym_gather(nb_sim *s, bool fuse_step, double dt)
+static int launch_sym_gather(nb_sim *s, bool fuse_step, double dt_kick, double dt_drift)
 {
     void *dst = s->path == StepPath::SYM ? s->partial : s->acc_full;
     return launch_gather(s, fuse_step, s->sym_rowbase_dev, s->sym_rowbase_dev + s->sym_tiles,     // [first row, first late row)
-                         s->sym_cov_begin_dev, s->sym_cov_dev, 0u, (uint32_t)s->n, dst, nullptr, dt);
+                         s->sym_cov_begin_dev, s->sym_cov_dev, 0u, (uint32_t)s->n, dst, nullptr, dt_kick, dt_drift);
 }
 
 // Sharded rank, after the reduce-scatter: acceleration of the owned block = acc_owned (the summed partials of all
@@ -1026,16 +1041,16 @@ static int launch_sym_gather_late(nb_sim *s, double dt)
     const uint32_t tiles = s->sym_tiles;
     return launch_gather(s, true, s->sym_rowbase_dev + tiles, s->sym_rowbase_dev + 2 * (size_t)tiles,   // [first late row, end row)
                          s->sym_cov_begin_dev + (tiles + 1), s->sym_cov_dev + s->sym_cov_late_off,      // coverage lists of the late segments
-                         (uint32_t)s->i_begin, (uint32_t)s->i_count, nullptr, s->acc_owned, dt);
+                         (uint32_t)s->i_begin, (uint32_t)s->i_count, nullptr, s->acc_owned, dt, dt);
 }
 
 // Whole-system symmetric force (+ optionally the kick/drift).
-static int launch_force_sym(nb_sim *s, bool fuse_step = false, double dt = 0.0)
+static int launch_force_sym(nb_sim *s, bool fuse_step = false, double dt_kick = 0.0, double dt_drift = 0.0)
 {
     int rc;
     if (s->ord.on && (rc = order_prepare(s))) return rc;
     if ((rc = launch_sym_items(s, 0, s->sym_items))) return rc;
-    return launch_sym_gather(s, fuse_step, dt);
+    return launch_sym_gather(s, fuse_step, dt_kick, dt_drift);
 }
 
 static int launch_force(nb_sim *s, const ForceJob &j)
@@ -1130,7 +1145,7 @@ static int step_begin_enqueue(nb_sim *s)
         // PARTIAL acceleration of every particle -> acc_full, which the host all-reduces before nb_step_finish
         int rc = launch_sym_items(s, 0, s->sym_items);
         if (rc) return rc;
-        return launch_sym_gather(s, false, 0.0);
+        return launch_sym_gather(s, false, 0.0, 0.0);
     }
     case StepPath::SYM_SHARDED: {
         // pairs inside my own block: no remote data needed.  On the side stream (ordered after everything
@@ -1158,6 +1173,7 @@ extern "C" int nb_step_begin(nb_sim *s, float dt)
     if (!s) return nb_fail(NB_EINVAL, "nb_step_begin: NULL handle");
     if (s->in_step) return nb_fail(NB_ESTATE, "nb_step_begin: previous step not finished");
     if (s->broken) return nb_fail(NB_ESTATE, "nb_step_begin: an earlier force launch of this handle was refused by the runtime; destroy the handle");
+    if (const char *name = composed_name(s->p.integrator)) return nb_fail(NB_EINVAL, "nb_step_begin: split stepping is the kick-drift integrator's (a %s handle steps with nb_step)", name);
     if (s->p.integrator != NB_INTEGRATOR_KICK_DRIFT) return nb_fail(NB_EINVAL, "nb_step_begin: split stepping is the kick-drift integrator's (a KDK handle steps with nb_step)");
     if (bind(s)) return NB_EHIP;
     s->pending_dt = dt > 0.0f ? dt : s->p.dt;
@@ -1185,7 +1201,7 @@ extern "C" int nb_step_mid(nb_sim *s)
         HIPCHK(hipEventRecord(s->ev_late, s->aux));
     }
     if (s->aux_local) HIPCHK(hipStreamWaitEvent(s->stream, s->ev_join, 0));   // the local items' slabs
-    if ((rc = launch_sym_gather(s, false, 0.0))) return rc;                   // partial acceleration of every particle -> acc_full
+    if ((rc = launch_sym_gather(s, false, 0.0, 0.0))) return rc;                   // partial acceleration of every particle -> acc_full
     s->mid_done = true;                                // only once everything was enqueued: a failed call can be seen and repeated
     return NB_OK;
 }
@@ -1216,7 +1232,7 @@ extern "C" int nb_step_finish(nb_sim *s)
         break;
     case StepPath::SYM:
         // whole system, symmetric kernel: the gather launch applies the kick and the drift itself
-        if ((rc = launch_force_sym(s, true, dt))) return rc;
+        if ((rc = launch_force_sym(s, true, dt, dt))) return rc;
         break;
     case StepPath::TWO_PHASE:
         if ((rc = launch_force(s, s->job_remote)) || (rc = integrate_slabs(s, s->slabs_two_phase, dt, dt, INTEG_KICK | INTEG_DRIFT))) return rc;
@@ -1255,6 +1271,56 @@ static int step_kdk(nb_sim *s, double dt)
     return NB_OK;
 }
 
+// ---- the composed integrators: NB_INTEGRATOR_DKD and NB_INTEGRATOR_FR4 (include/nbody.h) ----
+// One step of size h = a leading drift, then stages of (force at the current x; v += a k h; x += v d h).  A stage is the path's
+// own fused "force -> kick(dt_kick) -> drift(dt_drift)" launch with two different steps, so a DKD step costs a kick-drift step
+// plus one pass over positions and velocities, and an FR4 step three of them plus that pass.
+struct ComposedStage { double k, d; };
+constexpr double FR4_THETA = 1.3512071919596576340476878089715;           // 1 / (2 - 2^(1/3))
+constexpr double DKD_LEAD = 0.5, FR4_LEAD = 0.5 * FR4_THETA;
+static const ComposedStage DKD_STAGES[1] = {{1.0, 0.5}};
+static const ComposedStage FR4_STAGES[3] = {{FR4_THETA, 0.5 * (1.0 - FR4_THETA)}, {1.0 - 2.0 * FR4_THETA, 0.5 * (1.0 - FR4_THETA)}, {FR4_THETA, 0.5 * FR4_THETA}};
+
+// x <- x + v h for every body, pos[cur] -> pos[cur ^ 1]; flips cur.  The strict form where the handle's kick and drift are strict.
+static int launch_drift(nb_sim *s, double h)
+{
+    const uint32_t n = (uint32_t)s->n, g = (n + BLOCK - 1) / BLOCK;
+    const bool strict = s->tree ? s->p.rsqrt_mode == NB_RSQRT_QUAKE : s->p.sum_order == NB_SUM_SEQUENTIAL;
+    with_layout(s, [&](auto L) {
+        using real = typename decltype(L)::real;
+        using vec = typename decltype(L)::vec;
+        auto go = [&](auto kernel) {
+            kernel<<<g, BLOCK, 0, s->stream>>>((const vec *)s->pos[s->cur], (vec *)s->pos[s->cur ^ 1], (const vec *)s->vel, n, (real)h);
+        };
+        if constexpr (std::is_same_v<real, float> && !L.dims3)
+            if (strict) return go(drift<decltype(L), true>);        // fp32 2-D only, as launch_integrate
+        go(drift<decltype(L), false>);
+    });
+    HIPCHK(hipGetLastError());
+    s->cur ^= 1;
+    return NB_OK;
+}
+
+// Every coefficient * h is formed in double from the float h and rounded once to the handle's real (by the launches).  On a tree
+// handle a stage whose build fails applies neither its kick nor its drift (tree_integrate carries the positions over); the
+// leading drift is unconditional.  acc[] is left as the last stage's evaluation.
+static int step_composed(nb_sim *s, float h, double lead, const ComposedStage *stages, int nstages)
+{
+    const double hd = (double)h;
+    int rc;
+    if ((rc = launch_drift(s, lead * hd))) return rc;
+    for (int k = 0; k < nstages; ++k) {
+        const double hk = stages[k].k * hd, hx = stages[k].d * hd;
+        if (s->tree) { if ((rc = launch_tree_force(s)) || (rc = launch_tree_integrate(s, hk, hx, INTEG_KICK | INTEG_DRIFT))) return rc; }
+        else if (s->path == StepPath::SYM) { if ((rc = launch_force_sym(s, true, hk, hx))) return rc; }
+        else if ((rc = launch_force(s, s->job_all)) || (rc = integrate_slabs(s, s->slabs_all, hk, hx, INTEG_KICK | INTEG_DRIFT))) return rc;
+        s->cur ^= 1;
+    }
+    s->frame += 1;
+    s->acc_valid = false;
+    return NB_OK;
+}
+
 extern "C" int nb_step(nb_sim *s, float dt, int nsteps)
 {
     if (!s) return nb_fail(NB_EINVAL, "nb_step: NULL handle");
@@ -1266,6 +1332,13 @@ extern "C" int nb_step(nb_sim *s, float dt, int nsteps)
     for (int k = 0; k < nsteps; ++k) {
         int rc;
         if (s->p.integrator == NB_INTEGRATOR_KDK) { if ((rc = step_kdk(s, h))) return rc; continue; }
+        if (s->p.integrator == NB_INTEGRATOR_DKD || s->p.integrator == NB_INTEGRATOR_FR4) {
+            if (s->broken) return nb_fail(NB_ESTATE, "nb_step: an earlier force launch of this handle was refused by the runtime; destroy the handle");
+            const bool dkd = s->p.integrator == NB_INTEGRATOR_DKD;
+            if ((rc = step_composed(s, h, dkd ? DKD_LEAD : FR4_LEAD, dkd ? DKD_STAGES : FR4_STAGES, dkd ? 1 : 3))) return rc;
+            if (s->prof && s->ev_used.size() >= 2048 && (rc = prof_collect(s))) return rc;
+            continue;
+        }
         if ((rc = nb_step_begin(s, h))) return rc;
         if ((rc = nb_step_finish(s))) return rc;
         // keep the event list bounded on long runs
@@ -1819,6 +1892,9 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
         else snprintf(buf + len, buflen - len, " | force=direct");
         const size_t len2 = strlen(buf);
         if (s->bh.rel && len2 < buflen) snprintf(buf + len2, buflen - len2, " alpha=%.6g", (double)s->bh.alpha);
+        const size_t len3 = strlen(buf);
+        if (composed_name(s->p.integrator) && len3 < buflen)
+            snprintf(buf + len3, buflen - len3, " integrator=%s", s->p.integrator == NB_INTEGRATOR_DKD ? "dkd" : "fr4");
     }
     return NB_OK;
 }

@@ -1634,6 +1634,36 @@ void integrate(const typename L::vec *__restrict__ pos_cur,
 }
 
 // ---------------------------------------------------------------------------
+// drift — the lone drift of the composed integrators (NB_INTEGRATOR_DKD / _FR4, step_composed in nb_capi.hip): x_next = x + v h
+// for every body of a whole-system handle, in the form of kick_drift_loaded's drift: one fma per component, or STRICT (the
+// sequential order, the Quake tree: 2-D fp32) with the product and the sum individually rounded.  In 3-D the mass travels in .w.
+// ---------------------------------------------------------------------------
+template <typename L, bool STRICT>
+__global__ __launch_bounds__(BLOCK)
+void drift(const typename L::vec *__restrict__ pos_cur, typename L::vec *__restrict__ pos_next,
+           const typename L::vec *__restrict__ vel, uint32_t n, typename L::real h)
+{
+    static_assert(!(L::dims3 && STRICT), "the strict form is the 2-D sequential order's");
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const typename L::vec x = pos_cur[i], v = vel[i];
+    typename L::vec xn;
+    if constexpr (STRICT) {
+#pragma clang fp contract(off)
+        xn.x = x.x + v.x * h;
+        xn.y = x.y + v.y * h;
+    } else {
+        xn.x = __builtin_fma(v.x, h, x.x);
+        xn.y = __builtin_fma(v.y, h, x.y);
+        if constexpr (L::dims3) {
+            xn.z = __builtin_fma(v.z, h, x.z);
+            xn.w = x.w;                             // the mass travels with the position
+        }
+    }
+    pos_next[i] = xn;
+}
+
+// ---------------------------------------------------------------------------
 // sum_partials — in-process reduce-scatter of the symmetric sharded protocol: dst[k] = sum over the
 // handles (in handle order) of their partial acceleration of particle first + k.  `src` holds the
 // handles' acc_full pointers (peer-accessible device memory); T is the element type.

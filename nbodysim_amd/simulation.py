@@ -77,13 +77,16 @@ class Simulation:
         tree_alpha: Optional[float] = None,
         body_order: Optional[bool] = None,
     ):
-        """The last arguments (from ``uniform_mass`` on) are ``nb_params.flags`` and the launch-geometry tuning fields
+        """``integrator``: "kick_drift" (the reference's, first order), "kdk", or one of the composed integrators that every unsharded
+        handle takes, tree handles included: "dkd" (drift-kick-drift leapfrog: second order, reversible, one force evaluation per step)
+        and "fr4" (Forest-Ruth, fourth order, three evaluations per step; no ``extras``) — NB_INTEGRATOR_DKD / _FR4 of include/nbody.h.
+        The last arguments (from ``uniform_mass`` on) are ``nb_params.flags`` and the launch-geometry tuning fields
         (0 / True = the library's automatic choice); the library reads no environment variables.  ``mass_scaling``: False / None
         (default) = both per-pair mass multiplies, True = fold the masses into the pair geometry wherever representable
         (include/nbody.h, NB_FLAG_MASS_SCALING), "measured" = the library measures at upload whether folding is harmless for
         these bodies and folds only then (NB_FLAG_MASS_SCALING_MEASURED).  ``collide``: end every step with the reference's
         hard-sphere collisions (adds NB_EXTRA_COLLIDE to ``extras``; unsharded 2-D kick-drift only).  ``force``: "direct" (every pair) or "tree" (the reference's
-        Barnes-Hut quadtree with opening parameter ``theta``, NB_FORCE_TREE; unsharded 2-D fp32 kick-drift only).  ``tree_leaves``
+        Barnes-Hut quadtree with opening parameter ``theta``, NB_FORCE_TREE; unsharded 2-D fp32 with the kick-drift, DKD or FR4 integrator only).  ``tree_leaves``
         (``force="tree"`` only, ValueError otherwise): the convergent tree force, NB_FLAG_TREE_LEAVES — leaves that are not accepted
         contribute, so the result tends to the direct sum as ``theta`` -> 0; not the reference's arithmetic.  ``tree_quadrupole``
         (``force="tree"`` with ``tree_leaves=True`` only, ValueError otherwise): accepted cells add their second moment,
@@ -122,7 +125,8 @@ class Simulation:
         p.precision = {"fp32": L.NB_FP32, "fp64": L.NB_FP64}[precision]
         p.rsqrt_mode = {"exact": L.NB_RSQRT_EXACT, "quake": L.NB_RSQRT_QUAKE}[rsqrt]
         p.sum_order = {"tiled": L.NB_SUM_TILED, "sequential": L.NB_SUM_SEQUENTIAL}[order]
-        p.integrator = {"kick_drift": L.NB_INTEGRATOR_KICK_DRIFT, "kdk": L.NB_INTEGRATOR_KDK}[integrator]
+        p.integrator = {"kick_drift": L.NB_INTEGRATOR_KICK_DRIFT, "kdk": L.NB_INTEGRATOR_KDK, "dkd": L.NB_INTEGRATOR_DKD,
+                        "fr4": L.NB_INTEGRATOR_FR4}[integrator]
         p.extras = extras | (L.NB_EXTRA_COLLIDE if collide else 0)
         p.device = device
         p.j_slices = j_slices
