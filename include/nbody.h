@@ -265,7 +265,40 @@ enum { NB_INTEGRATOR_KICK_DRIFT = 0, /* Simulation.hpp:129-131,160-163 (referenc
           DKD applies NB_EXTRA_VCLAMP / NB_EXTRA_BOUNDARY in its one kick, at the midpoint position.  nb_step only (nb_step_begin
           refuses them, as it refuses KDK). */
        NB_INTEGRATOR_DKD = 2,        /* drift-kick-drift leapfrog */
-       NB_INTEGRATOR_FR4 = 3 };      /* Forest-Ruth 4th-order composition */
+       NB_INTEGRATOR_FR4 = 3,        /* Forest-Ruth 4th-order composition */
+       /* (4 is unassigned: nb_create refuses it with "bad integrator", like any value outside this enum) */
+       /* 4th-order Hermite predictor-corrector (Makino & Aarseth 1992): ONE force evaluation per step, and that evaluation returns
+          the acceleration and its time derivative, the jerk, from one sweep over the pairs.  With d = x_j - x_i, dv = v_j - v_i and
+          R^2 = d^2 + eps^2, the sums over ALL j:
+              a_i = sum_j m_j d / R^3        j_i = sum_j m_j ( dv / R^3 - 3 (d.dv) d / R^5 )
+          The pair of a body with itself adds exactly 0 to both sums.  A body on the position of another adds 0 to a and, with
+          eps > 0, the formula's m_j dv / eps^3 to j; on handles whose eps^2 is 0 in the sweep's arithmetic a pair with r^2 == 0
+          adds exactly 0 to both (1/r is set to 0 before any product, the rule of the one-sided force kernels).
+          One step of size h from the state (x, v) and the CARRIED pair (a0, j0):
+              predict   x_p = x + v h + a0 h^2/2 + j0 h^3/6        v_p = v + a0 h + j0 h^2/2
+              evaluate  (a1, j1) at (x_p, v_p)                                                      one launch
+              correct   v1 = v + (a0 + a1) h/2 + (j0 - j1) h^2/12      x1 = x + (v + v1) h/2 + (a0 - a1) h^2/12
+              carry     (a0, j0) <- (a1, j1);  acc[] = a1;  nb_frame grows by 1
+          h/2, h^2/2, h^3/6 and h^2/12 are formed in double from the float h that nb_step resolved and each rounded once to the
+          handle's real.  This is the standard PEC form: the next step starts from the evaluation at the predicted point.  A one-step
+          scheme: dt may change on every nb_step call with no loss of order.  The carried pair is state between steps and is INVALID
+          after nb_create, nb_upload and nb_accelerations: the first step after any of them first evaluates (a0, j0) at (x, v), so k
+          steps on a fresh handle are k + 1 launches and k afterwards.  Hence: nb_step(1) then nb_step(3) gives the bits of
+          nb_step(4); two handles of the same bodies agree bit for bit; a handle restarted from nb_dump (or re-uploaded from its own
+          nb_sync records) re-evaluates at the CORRECTED state and follows the original run to the scheme's order, NOT bit for bit;
+          acc of nb_sync is a1, "the last force evaluation".
+          ACCEPTED: unsharded direct-sum handles, fp32 and fp64, dims 2 and 3, the tiled sum, the hardware rsqrt.  Such a handle never
+          runs the symmetric kernels: it plans as a one-sided handle, nb_describe says symmetric=0 and ends with " integrator=hermite4".
+          IGNORED with it (they shape direct launches it never runs; range checks still apply): NB_FLAG_MASS_SCALING / _MEASURED /
+          NB_FLAG_NO_MASS_SCALING, NB_FLAG_NO_UNIFORM_MASS, NB_FLAG_BODY_ORDER / _NO_BODY_ORDER and the sym_* fields.  REFUSED by
+          nb_create (NB_EINVAL, naming HERMITE4 and the partner, before a device is looked for): NB_FORCE_TREE, shard_world > 1,
+          i_count < n, NB_FLAG_SHARD_SINGLE, NB_FLAG_SHARD_ALLREDUCE, any extras (the clamp, the damped boundary and the collisions are
+          not differentiable: there is no jerk of them), NB_SUM_SEQUENTIAL, NB_RSQRT_QUAKE.  nb_step only (nb_step_begin refuses it).
+          ARITHMETIC of the evaluation (nb_jerks below returns it): fp32 handles add the terms of 64 consecutive j in float32 and those
+          runs in float64, in a fixed order; fp64 handles add in j order.  The order does not depend on timing or launch geometry.
+          MEMORY beyond a one-sided handle: a jerk array and a predicted-velocity array of one element each (8 B per body each for fp32
+          2-D, 16 B for fp64 2-D and fp32 3-D, 32 B for fp64 3-D) and the evaluation's rows, 16 dims bytes per body. */
+       NB_INTEGRATOR_HERMITE4 = 5 };
 
 /* nb_params.flags bit mask: algorithm switches (all 0 = the fast defaults) */
 enum { NB_FLAG_NO_SYMMETRY     = 1,   /* one-sided kernels only (every ordered pair evaluated); a sharded
@@ -1092,6 +1125,17 @@ int nb_radial_profiles(nb_sim *s, const float *centers, const double *vcenters, 
  * one (nb_profile_read). */
 #define NB_FIELD_POINTS_MAX 4194304
 int nb_field(nb_sim *s, const float *points, size_t npoints, double *phi, double *acc);
+
+/* Acceleration and jerk of every body at the handle's CURRENT positions and velocities, as fp64: the evaluation of
+ * NB_INTEGRATOR_HERMITE4 (see the enum), by the step's own kernel.  What a time-step criterion starts from: dt ~ eta |a| / |j|.
+ * acc, jerk: dims * n doubles each, packed per body (nb_field's acc plane); either may be NULL, both NULL is NB_EINVAL.
+ * NB_INTEGRATOR_HERMITE4 handles only: NB_EINVAL on any other, naming its integrator.  NB_ESTATE while a split step is in flight.
+ * It touches nothing: acc[], the carried pair, positions, velocities and the frame stay as they are, and the next step is
+ * bit-identical to one on a handle that never called this.  Either plane alone has the bits it has in the joint call (both are
+ * always computed).  Note that between steps acc[] holds a1, the evaluation at the PREDICTED point, while this call evaluates at
+ * the corrected state.  The call synchronises; the planes move out like nb_field's (page-locked destinations directly, others through
+ * the query calls' shared staging buffer).  With nb_profile_enable the sweep counts as one force launch. */
+int nb_jerks(nb_sim *s, double *acc, double *jerk);
 
 /* NB_FLAG_TREE_RELATIVE: set alpha of the acceleration-relative opening test between steps (the evaluations already enqueued keep
  * theirs).  alpha must be finite and >= 0 (NB_EINVAL otherwise); 0 switches the test off.  NB_ESTATE on a handle created without

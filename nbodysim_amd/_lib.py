@@ -26,6 +26,7 @@ NB_RSQRT_EXACT, NB_RSQRT_QUAKE = 0, 1
 NB_SUM_TILED, NB_SUM_SEQUENTIAL = 0, 1
 NB_EXTRA_VCLAMP, NB_EXTRA_BOUNDARY, NB_EXTRA_COLLIDE = 1, 2, 4
 NB_INTEGRATOR_KICK_DRIFT, NB_INTEGRATOR_KDK, NB_INTEGRATOR_DKD, NB_INTEGRATOR_FR4 = 0, 1, 2, 3
+NB_INTEGRATOR_HERMITE4 = 5                      # 4 is unassigned
 NB_FORCE_DIRECT, NB_FORCE_TREE = 0, 1
 NB_POS_CURRENT, NB_POS_NEXT = 0, 1
 NB_SHARD_NONE, NB_SHARD_ALLGATHER, NB_SHARD_SYMMETRIC, NB_SHARD_ALLREDUCE = 0, 1, 2, 3
@@ -254,6 +255,7 @@ PROTOTYPES = {
     "nb_pair_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "nb_radial_profiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p]),
     "nb_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "nb_jerks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nb_frame": (C.c_uint64, [C.c_void_p]),
     "nb_count": (C.c_size_t, [C.c_void_p]),
     "nb_owned_begin": (C.c_size_t, [C.c_void_p]),

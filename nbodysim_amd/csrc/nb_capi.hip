@@ -140,6 +140,7 @@ static bool order_wanted(const nb_sim *s)
 static bool sym_eligible(const nb_sim *s)
 {
     if (s->p.flags & NB_FLAG_NO_SYMMETRY) return false;
+    if (s->p.integrator == NB_INTEGRATOR_HERMITE4) return false;      // its one force kernel is one-sided (nb_hermite.hip.h)
     if (s->p.sum_order != NB_SUM_TILED || needs_guard(s)) return false;
     if (s->fp64 && s->p.rsqrt_mode != NB_RSQRT_EXACT) return false;
     if (s->p.integrator != NB_INTEGRATOR_KICK_DRIFT && s->i_count != s->n) return false;
@@ -620,6 +621,7 @@ static int copy_plane(nb_sim *s, void *dst, const void *src, size_t bytes) { ret
 #include "nb_pair_counts_host.hip.h"
 #include "nb_profiles_host.hip.h"
 #include "nb_field_host.hip.h"
+#include "nb_hermite_host.hip.h"
 #include "nb_order_host.hip.h"
 
 // what every synchronising call reports once: a collision step over capacity, a failed tree build
@@ -635,7 +637,8 @@ static int do_upload(nb_sim *s, const nb_body *in)
     // Equal masses (the synthetic Plummer workload, most N-body ICs) let the force kernel hoist the
     // per-pair mass multiply: 8 instead of 9 packed ops per two pairs.  NB_FLAG_NO_UNIFORM_MASS disables it.
     // (a tree handle has none of the direct-sum specialisations: the flags that select them are ignored, include/nbody.h)
-    s->uniform_mass = s->n > 0 && !s->tree && !(s->p.flags & NB_FLAG_NO_UNIFORM_MASS) && s->p.sum_order == NB_SUM_TILED;
+    // (nor has a Hermite handle: its one pair kernel takes individual masses)
+    s->uniform_mass = s->n > 0 && !s->tree && !hermite(s) && !(s->p.flags & NB_FLAG_NO_UNIFORM_MASS) && s->p.sum_order == NB_SUM_TILED;
     for (size_t i = 1; s->uniform_mass && i < s->n; ++i)
         if (memcmp(&in[i].mass, &in[0].mass, sizeof(float)) != 0) s->uniform_mass = false;
     s->um_mass = in[0].mass;
@@ -650,7 +653,7 @@ static int do_upload(nb_sim *s, const nb_body *in)
     s->mass_scaled = false;
     s->mass_scaling_dev = -1.0f;
     bool scalable = false;
-    if (!s->tree && !s->uniform_mass && s->p.sum_order == NB_SUM_TILED && !needs_guard(s) && !s->fp64 && !s->dims3 &&
+    if (!s->tree && !hermite(s) && !s->uniform_mass && s->p.sum_order == NB_SUM_TILED && !needs_guard(s) && !s->fp64 && !s->dims3 &&
         s->p.rsqrt_mode == NB_RSQRT_EXACT && (s->p.flags & (NB_FLAG_MASS_SCALING | NB_FLAG_MASS_SCALING_MEASURED)) && !(s->p.flags & NB_FLAG_NO_MASS_SCALING)) {
         double mmin = HUGE_VAL, mmax = 0.0;
         bool finite = true;
@@ -687,6 +690,7 @@ static int do_upload(nb_sim *s, const nb_body *in)
     if (s->collide) { const int rc = collide_classify(s, in); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(s->stream));  // `in` may be pageable and freed by the caller
     s->acc_valid = false;
+    s->herm.valid = false;                    // a Hermite handle evaluates (a0, j0) at the uploaded state before its next step
     if (auto_scaling) { const int rc = choose_mass_scaling(s); if (rc) return rc; }
     // the resident-slot count behind the static / dynamic item split belongs to ONE kernel instantiation (its VGPR count sets the
     // occupancy): the check above launches MM_GENERAL whatever the verdict, and a re-upload can flip uniform_mass — ask again
@@ -719,7 +723,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     if (p.precision != NB_FP32 && p.precision != NB_FP64) { nb_set_error("nb_create: bad precision %d", p.precision); return nullptr; }
     if (p.rsqrt_mode != NB_RSQRT_EXACT && p.rsqrt_mode != NB_RSQRT_QUAKE) { nb_set_error("nb_create: bad rsqrt_mode %d", p.rsqrt_mode); return nullptr; }
     if (p.sum_order != NB_SUM_TILED && p.sum_order != NB_SUM_SEQUENTIAL) { nb_set_error("nb_create: bad sum_order %d", p.sum_order); return nullptr; }
-    if (p.integrator < NB_INTEGRATOR_KICK_DRIFT || p.integrator > NB_INTEGRATOR_FR4) { nb_set_error("nb_create: bad integrator %d", p.integrator); return nullptr; }
+    if (p.integrator < NB_INTEGRATOR_KICK_DRIFT || (p.integrator > NB_INTEGRATOR_FR4 && p.integrator != NB_INTEGRATOR_HERMITE4)) { nb_set_error("nb_create: bad integrator %d", p.integrator); return nullptr; }
     if (p.precision == NB_FP64 && (p.rsqrt_mode == NB_RSQRT_QUAKE || p.sum_order == NB_SUM_SEQUENTIAL)) {
         nb_set_error("nb_create: quake rsqrt / sequential order are fp32 (reference arithmetic) modes");
         return nullptr;
@@ -734,6 +738,16 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
                         : (p.extras && p.integrator == NB_INTEGRATOR_FR4) ? "extras (its middle kick is negative: the velocity clamp and the damped boundary "
                                                                             "are not maps that can be run backwards)" : nullptr;
         if (why) { nb_set_error("nb_create: the %s integrator steps whole unsharded handles; not supported with %s", name, why); return nullptr; }
+    }
+    if (p.integrator == NB_INTEGRATOR_HERMITE4) {
+        // the Hermite integrator (step_hermite, nb_hermite_host.hip.h): whole unsharded direct-sum handles, tiled sum, hardware rsqrt, no extras
+        const char *why = p.force == NB_FORCE_TREE ? "NB_FORCE_TREE (a walk has no jerk)" : p.shard_world > 1 ? "shard_world > 1"
+                        : (p.i_count != 0 && p.i_count < n) ? "i_count < n"
+                        : (p.flags & NB_FLAG_SHARD_SINGLE) ? "NB_FLAG_SHARD_SINGLE" : (p.flags & NB_FLAG_SHARD_ALLREDUCE) ? "NB_FLAG_SHARD_ALLREDUCE"
+                        : p.extras ? "extras (the velocity clamp, the damped boundary and the collisions are not differentiable: there is no jerk of them)"
+                        : p.sum_order == NB_SUM_SEQUENTIAL ? "NB_SUM_SEQUENTIAL"
+                        : p.rsqrt_mode == NB_RSQRT_QUAKE ? "NB_RSQRT_QUAKE (the reference's arithmetic has no Hermite to match)" : nullptr;
+        if (why) { nb_set_error("nb_create: the HERMITE4 integrator steps whole unsharded direct-sum handles; not supported with %s", why); return nullptr; }
     }
     if (p.extras & NB_EXTRA_COLLIDE) {
         const char *why = p.dims == 3 ? "dims = 3" : p.integrator != NB_INTEGRATOR_KICK_DRIFT ? "the KDK integrator"
@@ -867,7 +881,7 @@ extern "C" nb_sim *nb_create(const nb_body *init, size_t n, const nb_params *par
     s->collide = (p.extras & NB_EXTRA_COLLIDE) != 0;
     s->ord.on = order_wanted(s);
     if ((symmetric(s) && plan_sym(s) != NB_OK) || (s->ord.on && order_alloc(s) != NB_OK) || (s->collide && collide_alloc(s) != NB_OK) ||
-        (s->tree && tree_alloc(s) != NB_OK) || do_upload(s, init) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }     // (nb_fail has said why)
+        (s->tree && tree_alloc(s) != NB_OK) || (hermite(s) && hermite_alloc(s) != NB_OK) || do_upload(s, init) != NB_OK) { free_all(s); (void)hipGetLastError(); return nullptr; }     // (nb_fail has said why)
     return s;
 }
 
@@ -1173,6 +1187,7 @@ extern "C" int nb_step_begin(nb_sim *s, float dt)
     if (!s) return nb_fail(NB_EINVAL, "nb_step_begin: NULL handle");
     if (s->in_step) return nb_fail(NB_ESTATE, "nb_step_begin: previous step not finished");
     if (s->broken) return nb_fail(NB_ESTATE, "nb_step_begin: an earlier force launch of this handle was refused by the runtime; destroy the handle");
+    if (hermite(s)) return nb_fail(NB_EINVAL, "nb_step_begin: split stepping is the kick-drift integrator's (a HERMITE4 handle steps with nb_step)");
     if (const char *name = composed_name(s->p.integrator)) return nb_fail(NB_EINVAL, "nb_step_begin: split stepping is the kick-drift integrator's (a %s handle steps with nb_step)", name);
     if (s->p.integrator != NB_INTEGRATOR_KICK_DRIFT) return nb_fail(NB_EINVAL, "nb_step_begin: split stepping is the kick-drift integrator's (a KDK handle steps with nb_step)");
     if (bind(s)) return NB_EHIP;
@@ -1339,6 +1354,11 @@ extern "C" int nb_step(nb_sim *s, float dt, int nsteps)
             if (s->prof && s->ev_used.size() >= 2048 && (rc = prof_collect(s))) return rc;
             continue;
         }
+        if (hermite(s)) {
+            if ((rc = step_hermite(s, h))) return rc;
+            if (s->prof && s->ev_used.size() >= 2048 && (rc = prof_collect(s))) return rc;
+            continue;
+        }
         if ((rc = nb_step_begin(s, h))) return rc;
         if ((rc = nb_step_finish(s))) return rc;
         // keep the event list bounded on long runs
@@ -1354,6 +1374,7 @@ extern "C" int nb_accelerations(nb_sim *s)
     if (bind(s)) return NB_EHIP;
     int rc;
     if (s->tree) return (rc = launch_tree_force(s)) ? rc : launch_tree_integrate(s, 0.0, 0.0, 0);
+    s->herm.valid = false;            // acc[] is rewritten: a Hermite handle's carried pair is gone, its next step evaluates again
     // job_all: a sharded or replicated handle has no whole-system plan, so this takes the one-sided kernels
     if ((rc = launch_force(s, s->job_all))) return rc;
     return integrate_slabs(s, s->slabs_all, 0.0, 0.0, 0);   // acc <- sum of slabs, nothing else
@@ -1895,6 +1916,7 @@ extern "C" int nb_describe(nb_sim *s, char *buf, size_t buflen)
         const size_t len3 = strlen(buf);
         if (composed_name(s->p.integrator) && len3 < buflen)
             snprintf(buf + len3, buflen - len3, " integrator=%s", s->p.integrator == NB_INTEGRATOR_DKD ? "dkd" : "fr4");
+        else if (hermite(s) && len3 < buflen) snprintf(buf + len3, buflen - len3, " integrator=hermite4");
     }
     return NB_OK;
 }

@@ -373,7 +373,7 @@ static int read_header(FILE *f, const char *path, nb_file_header *h)
     if (fseek(f, (long)sizeof *h, SEEK_SET) != 0) return nb_fail(NB_EIO, "%s: cannot seek", path);
     if ((h->precision != NB_FP32 && h->precision != NB_FP64) || (h->rsqrt_mode != NB_RSQRT_EXACT && h->rsqrt_mode != NB_RSQRT_QUAKE) ||
         (h->sum_order != NB_SUM_TILED && h->sum_order != NB_SUM_SEQUENTIAL) ||
-        h->integrator < NB_INTEGRATOR_KICK_DRIFT || h->integrator > NB_INTEGRATOR_FR4 ||
+        h->integrator < NB_INTEGRATOR_KICK_DRIFT || (h->integrator > NB_INTEGRATOR_FR4 && h->integrator != NB_INTEGRATOR_HERMITE4) ||
         (h->extras & ~(NB_EXTRA_VCLAMP | NB_EXTRA_BOUNDARY | NB_EXTRA_COLLIDE)) || !(h->eps >= 0.0f))
         return nb_fail(NB_EFORMAT, "%s: header holds parameters outside their enums", path);
     return NB_OK;

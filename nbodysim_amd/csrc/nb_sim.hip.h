@@ -2,7 +2,7 @@
 // device binding, the dispatchers from run-time choices to template arguments.  Included by nb_capi.hip (the one device
 // translation unit) ahead of the host sides of the subsystems, nb_collide_host.hip.h, nb_tree_host.hip.h, nb_raster_host.hip.h,
 // nb_potential_host.hip.h, nb_neighbors_host.hip.h, nb_groups_host.hip.h, nb_group_catalog_host.hip.h, nb_group_binding_host.hip.h, nb_pair_counts_host.hip.h,
-// nb_profiles_host.hip.h, nb_field_host.hip.h and nb_order_host.hip.h.
+// nb_profiles_host.hip.h, nb_field_host.hip.h, nb_hermite_host.hip.h and nb_order_host.hip.h.
 #pragma once
 #include "nbody.h"
 #include "nbody_debug.h"
@@ -19,6 +19,7 @@
 #include "nb_pair_counts.hip.h"
 #include "nb_profiles.hip.h"
 #include "nb_field.hip.h"
+#include "nb_hermite.hip.h"
 #include "nb_order.hip.h"
 
 #include <hip/hip_runtime.h>
@@ -321,6 +322,14 @@ struct nb_sim {
         uint64_t bytes = 0;                    // bytes `buf` holds: 8 (dims + 1) + 4 dims per point
         void *buf = nullptr;                   // the call's phi plane, then its acc plane, then its points
     } fld;
+
+    // NB_INTEGRATOR_HERMITE4 (nb_hermite.hip.h): nothing in `herm` is allocated for a handle of another integrator
+    struct Hermite {
+        bool valid = false;                    // acc[] and jerk hold the carried pair (a0, j0): false after nb_create / nb_upload
+        void *jerk = nullptr;                  // the carried jerk, one vec per body
+        void *vpred = nullptr;                 // the predicted velocities, one vec per body (the predicted positions go to pos[cur ^ 1])
+        double *rows = nullptr;                // the evaluation's rows: the acc plane, then the jerk plane, dims doubles per body each
+    } herm;
 
     // body order of the whole-system symmetric path (nb_order.hip.h): nothing in `ord` is allocated unless `on`
     struct Order {

@@ -6,7 +6,7 @@
  * compute in libnbody_hip.so.
  *
  *   nbody_main [-n N] [-s steps] [-dt DT] [-eps EPS] [-seed S] [-fp64] [-quake]
- *              [-sequential] [-kdk | -dkd | -fr4] [-dump FILE] [-load FILE] [-sync-every K]
+ *              [-sequential] [-kdk | -dkd | -fr4 | -hermite] [-dump FILE] [-load FILE] [-sync-every K]
  *              [-reference-ics]  the reference's own start: Simulation()'s 25 000-body disc (or -n N of it),
  *                            eps = 1, dt = 0.01, velocity clamp + soft boundary (Simulation.hpp:58-65,116-163)
  *              [-tree [theta]]  the reference's Barnes-Hut force (NB_FORCE_TREE; theta defaults to 1, Simulation.hpp:59)
@@ -156,6 +156,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "-kdk")) p.integrator = NB_INTEGRATOR_KDK;
         else if (!strcmp(argv[i], "-dkd")) p.integrator = NB_INTEGRATOR_DKD;
         else if (!strcmp(argv[i], "-fr4")) p.integrator = NB_INTEGRATOR_FR4;
+        else if (!strcmp(argv[i], "-hermite")) p.integrator = NB_INTEGRATOR_HERMITE4;
         else if (!strcmp(argv[i], "-collide")) p.extras |= NB_EXTRA_COLLIDE;
         else if (!strcmp(argv[i], "-tree")) {
             p.force = NB_FORCE_TREE;

@@ -80,6 +80,8 @@ class Simulation:
         """``integrator``: "kick_drift" (the reference's, first order), "kdk", or one of the composed integrators that every unsharded
         handle takes, tree handles included: "dkd" (drift-kick-drift leapfrog: second order, reversible, one force evaluation per step)
         and "fr4" (Forest-Ruth, fourth order, three evaluations per step; no ``extras``) — NB_INTEGRATOR_DKD / _FR4 of include/nbody.h.
+        "hermite4": the 4th-order Hermite predictor-corrector, one evaluation of acceleration and jerk per step (NB_INTEGRATOR_HERMITE4:
+        unsharded direct-sum handles, tiled sum, hardware rsqrt, no ``extras``; ``dt`` may change from step to step; see ``jerks``).
         The last arguments (from ``uniform_mass`` on) are ``nb_params.flags`` and the launch-geometry tuning fields
         (0 / True = the library's automatic choice); the library reads no environment variables.  ``mass_scaling``: False / None
         (default) = both per-pair mass multiplies, True = fold the masses into the pair geometry wherever representable
@@ -126,7 +128,7 @@ class Simulation:
         p.rsqrt_mode = {"exact": L.NB_RSQRT_EXACT, "quake": L.NB_RSQRT_QUAKE}[rsqrt]
         p.sum_order = {"tiled": L.NB_SUM_TILED, "sequential": L.NB_SUM_SEQUENTIAL}[order]
         p.integrator = {"kick_drift": L.NB_INTEGRATOR_KICK_DRIFT, "kdk": L.NB_INTEGRATOR_KDK, "dkd": L.NB_INTEGRATOR_DKD,
-                        "fr4": L.NB_INTEGRATOR_FR4}[integrator]
+                        "fr4": L.NB_INTEGRATOR_FR4, "hermite4": L.NB_INTEGRATOR_HERMITE4}[integrator]
         p.extras = extras | (L.NB_EXTRA_COLLIDE if collide else 0)
         p.device = device
         p.j_slices = j_slices
@@ -478,6 +480,18 @@ class Simulation:
         L.check("nb_field", self._lib.nb_field(self._h, p.ctypes.data, p.shape[0], by["phi"].ctypes.data if phi else None,
                                                by["acc"].ctypes.data if acc else None), self._lib)
         return tuple(planes) if len(planes) == 2 else planes[0]
+
+    def jerks(self, acc: bool = True, jerk: bool = True):
+        """Acceleration and jerk (its time derivative) of every body at the current positions and velocities (``nb_jerks``;
+        ``integrator="hermite4"`` handles only; synchronises; changes nothing of the handle).  Returns ``acc`` or ``jerk`` (float64,
+        ``(n, dims)``) or the pair ``(acc, jerk)``, as asked for."""
+        if not (acc or jerk):
+            raise ValueError("jerks: at least one of acc and jerk must be asked for")
+        dims = 3 if self._params.dims == 3 else 2
+        planes = [np.empty((self.n, dims), dtype=np.float64) if want else None for want in (acc, jerk)]
+        L.check("nb_jerks", self._lib.nb_jerks(self._h, *(None if a is None else a.ctypes.data for a in planes)), self._lib)
+        got = [a for a in planes if a is not None]
+        return tuple(got) if len(got) == 2 else got[0]
 
     def set_tree_alpha(self, alpha: float) -> None:
         """Set alpha of the acceleration-relative opening test (``nb_tree_alpha``; ``tree_alpha`` handles only) between steps."""
